@@ -12,7 +12,13 @@ torch.distributed is used only for the barrier and the max-over-ranks of the tim
 
 Prints ONE COMPACT JSON line (< 4 KB, tools/bench_line.py) on rank 0 as the LAST line of stdout -- the driver contract's keys + `roofline`,
 `cpu_baseline`, `parity`, `value_end_to_end` and one-number summaries of the other legs; the run's FULL record (everything below with its notes) goes
-to --full-json (default <workdir>/bench_full_<workload>.json) and as one-liners to stderr.  The objects of the full record:
+to --full-json (default <workdir>/bench_full_<workload>.json) and as one-liners to stderr.
+
+A plain run sets up, warms up, times the steps, writes the last step's output if --dump-outputs is given and prints the line: `cpu_baseline`,
+`parity`, `end_to_end`, `binding` and the side workloads (`config5`, `config2`) are null there.  --full runs them as well (they take minutes).
+The synthetic genome, its index and the timed chunk (~22 GB at 3100 Mbp) are cached in --workdir and checked before use: files cut short are
+made again.  `bench.py --prepare-only` fills the cache (build() does so on a GPU host) so that a run does not spend ~40 s building the index.
+The objects of the full record (cpu_baseline, parity, end_to_end: --full only):
   roofline     -- the FM-index seeding kernel against the HBM peak, from ALGORITHMIC bytes (128 B per backwardExt,
                   SURVEY.md section 8(d)) over its HIP-event-timed launches inside the timed region; `achieved_counter` is the
                   same with the HBM bytes the PMC passes measured (profiles/)
@@ -47,6 +53,41 @@ from tools import bench_line                                                    
 from tools.bench_legs import (CONFIG5_READS, HBM_PEAK_GBS, ONT2D, RANDOM_LINE_GLPS, alnregs_records, bench_bsw, binding_leg, cpu_baseline,      # noqa: E402,F401
                               cpu_baseline_from, end_to_end, host_threads, log, make_extension_pairs, parity_gate, pe_chunk, prepare_genome,
                               ref_binary, regs_records, run_reference_mem, run_side_workloads, s1_binding_leg, sam_gate, sam_lines, side_workload)
+
+SEED = 20260924
+DUMP_SEED = 7919                 # the reads (pairs) whose outputs --dump-outputs writes: a fixed sample, the same in every run
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_regs(d, regs, reg_off):
+    """--dump-outputs of the pe150 / ont2d workloads: the regs a caller of batch_run receives (bm2.Context.batch_download) for a fixed, seeded
+    sample of the chunk's reads -> <d>/reads.npy (read numbers), n_regs.npy (regs per read) and reg_<field>.npy (the regs of those reads in read
+    order; rb / re float64, the rest float32: exact for these values)."""
+    n_reads = len(reg_off) - 1
+    rng = np.random.default_rng(DUMP_SEED)
+    reads = np.sort(rng.choice(n_reads, size=min(n_reads, 65536), replace=False)) if n_reads else np.zeros(0, np.int64)
+    cnt = np.diff(reg_off)[reads]
+    wide, narrow = ("rb", "re"), ("qb", "qe", "rid", "score", "truesc", "w", "seedcov", "seedlen0", "frac_rep")
+    per_reg = 8 * len(wide) + 4 * len(narrow)
+    keep = int(np.searchsorted(np.cumsum(16 + cnt * per_reg), DUMP_MAX_BYTES, side="right"))      # (a bound, never reached by these workloads)
+    reads, cnt = reads[:keep], cnt[:keep]
+    idx = np.concatenate([np.arange(reg_off[r], reg_off[r + 1]) for r in reads]) if len(reads) else np.zeros(0, np.int64)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "reads.npy"), reads.astype(np.float64))
+    np.save(os.path.join(d, "n_regs.npy"), cnt.astype(np.float64))
+    for f in wide:
+        np.save(os.path.join(d, "reg_%s.npy" % f), regs[f][idx].astype(np.float64))
+    for f in narrow:
+        np.save(os.path.join(d, "reg_%s.npy" % f), regs[f][idx].astype(np.float32))
+    log("outputs of the last step: regs of %d of %d reads (%d regs) -> %s" % (len(reads), n_reads, len(idx), d))
+
+
+def prepare_inputs(a):
+    """the genome + index and the timed chunk of the pe150 workload in a.workdir (cached there) -> (prefix, contigs, seqs)"""
+    from tools import dist_util
+    prefix, contigs = prepare_genome(a.workdir, a.genome_mbp, SEED)
+    seqs = pe_chunk(a.workdir, contigs, dist_util.shard_seed(SEED, 0), a.reads or 1000000, a.read_len)
+    return prefix, contigs, seqs
 
 
 def main():
@@ -84,6 +125,14 @@ def main():
                          "10 x 10 chunks of 1 M reads, is BASELINE config 4's read count -- 100 M reads -- through one GPU)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: ONE chunk of --reads reads is cut at multiples of 512 over the ranks (SURVEY.md 8(e)) instead of one chunk per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure: parity gates against the compiled reference, CPU baseline, end-to-end FASTQ -> SAM, "
+                         "the drop-in binaries, configs 5 and 2 as side workloads (off: the run times the steps and prints the line, those objects null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (a fixed, seeded sample of its reads' regs; "
+                         "bsw: of its pairs' scores)")
+    ap.add_argument("--prepare-only", action="store_true",
+                    help="build the cached inputs (synthetic genome, index, timed chunk) in --workdir and exit: no GPU needed")
     ap.add_argument("--workdir", default=os.environ.get("BM2_BENCH_WORKDIR", "/tmp/bm2_bench"))
     ap.add_argument("--full-json", default=os.environ.get("BM2_BENCH_FULL_JSON"),
                     help="where the run's FULL record goes (every leg with its notes, per-kernel tables, the side workloads' own records); default "
@@ -94,6 +143,13 @@ def main():
     a = ap.parse_args()
     if not a.full_json:
         a.full_json = os.path.join(a.workdir, "bench_full_%s.json" % a.workload)
+    if not a.full:
+        a.no_cpu_baseline = a.no_parity = a.no_e2e = a.no_binding = a.no_binding_s1 = a.no_side_workloads = True
+    if a.prepare_only:
+        os.makedirs(a.workdir, exist_ok=True)
+        prefix, _, seqs = prepare_inputs(a)
+        log("inputs ready: %s, timed chunk of %d reads" % (prefix, len(seqs)))
+        return
     t_start = time.time()
     hung = False
 
@@ -111,7 +167,7 @@ def main():
     elif not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (libbm2 has no CPU fallback)")
     os.makedirs(a.workdir, exist_ok=True)
-    seed = 20260924
+    seed = SEED
     # Config 2 AS WORDED (seeding on the host, banded SW on the GPU, inside the reference's own program: `bwa-mem2.bm2s1 mem`) is timed FIRST, before this
     # process opens the device: the binding's small device batches take 6.45 s per million reads with the GPU to themselves and 8.3-8.7 s beside a process
     # that merely holds contexts and queues there (profiles/r05e_*, r05z_*: closing this process's bm2 context did not help -- torch's stays).  A user of
@@ -240,6 +296,8 @@ def main():
             reads_timed += len(l_k)
             for name, ms in ctx.batch_kernel_ms():
                 kms[name] = kms.get(name, 0.0) + ms
+        if a.dump_outputs and rank == 0 and a.steps > 0:
+            dump_regs(a.dump_outputs, *ctx.batch_download())
         if a.steps % n_distinct:                              # (the gate below compares chunk 0's regs: make it the resident one)
             ctx.batch_upload(enc, off, ln); ctx.batch_run(opt)
         dt = dist_util.max_over_ranks(dt_local, world, "cpu" if emu else "cuda")
@@ -256,6 +314,8 @@ def main():
         torch.cuda.synchronize()
         dist_util.barrier(world)
         dt = dist_util.max_over_ranks(time.perf_counter() - t0, world, "cpu" if emu else "cuda")
+        if a.dump_outputs and rank == 0 and a.steps > 0:      # (the context of the last step: the steps go round the resident chunks)
+            dump_regs(a.dump_outputs, *run_ctx[(a.steps - 1) % n_res].batch_download())
     st = ctx.batch_stats()
     parts = ctx.batch_parts() if hasattr(ctx, "batch_parts") else 1      # (a chunk runs as `parts` parts beside each other: the per-kernel times are summed over them)
     if n_res > 1:                                            # work counters: the mean over the chunks that ran (they differ by a fraction of a per cent)

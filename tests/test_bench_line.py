@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 from tools import bench_line  # noqa: E402
 
 CANNED = sorted(glob.glob(os.path.join(ROOT, "profiles", "r05zzz_bench*.json")) + glob.glob(os.path.join(ROOT, "profiles", "r04zz_bench_as_driver.json"))
-                + glob.glob(os.path.join(ROOT, "profiles", "r05*_bench_bsw*.json"))[:1] + glob.glob(os.path.join(ROOT, "profiles", "r06*_bench_full*.json")))
+                + sorted(glob.glob(os.path.join(ROOT, "profiles", "r05*_bench_bsw*.json"))) + glob.glob(os.path.join(ROOT, "profiles", "r06*_bench_full*.json")))
 
 
 def _strict(s):
@@ -117,3 +117,55 @@ def test_bench_main_ends_in_emit():
     prints = [m.group(0) for m in re.finditer(r"^\s*print\(.*$", src, re.M)]
     assert all("file=sys.stderr" in p for p in prints), prints
     assert src.count("bench_line.emit(") == 2                # the pe150 / ont2d line and config 2's
+
+
+def test_dump_outputs_is_a_fixed_sample_of_the_regs_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: the same reads every run, their regs exact (rb / re beyond 2^32), float32 / float64 files, < 64 MB"""
+    import numpy as np
+    import bench
+    import bm2
+    rng = np.random.default_rng(3)
+    cnt = rng.integers(0, 5, size=1000000)
+    reg_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    regs = np.zeros(int(reg_off[-1]), bm2.REG_DT)
+    regs["rb"] = rng.integers(0, 6200000000, size=len(regs))
+    regs["re"] = regs["rb"] + 150
+    regs["score"] = rng.integers(0, 151, size=len(regs))
+    regs["frac_rep"] = rng.random(len(regs)).astype(np.float32)
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_regs(a, regs, reg_off)
+    bench.dump_regs(b, regs, reg_off)
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) and "reg_rb.npy" in names and "n_regs.npy" in names
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in names) < 64 << 20
+    for f in names:
+        x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    reads = np.load(os.path.join(a, "reads.npy")).astype(np.int64)
+    assert len(reads) == 65536 and (np.diff(reads) > 0).all()
+    n = np.load(os.path.join(a, "n_regs.npy")).astype(np.int64)
+    assert (n == cnt[reads]).all()
+    idx = np.concatenate([np.arange(reg_off[r], reg_off[r + 1]) for r in reads])
+    assert (np.load(os.path.join(a, "reg_rb.npy")).astype(np.int64) == regs["rb"][idx]).all()
+    assert (np.load(os.path.join(a, "reg_frac_rep.npy")) == regs["frac_rep"][idx]).all()
+
+
+def test_a_cut_cached_index_is_not_taken_for_a_complete_one(tmp_path):
+    """bench.py's cache: the index files are checked against their own headers before use (a copy of the cache cut short is built again)"""
+    import shutil
+    from tools import bench_legs
+    pre = str(tmp_path / "g.fa")
+    for ext in (".0123", ".amb", ".ann", ".bwt.2bit.64", ".pac"):
+        shutil.copy(os.path.join(ROOT, "tests", "golden", "g20k_l76.fa" + ext), pre + ext)
+    assert bench_legs.index_complete(pre)
+    for ext in (".bwt.2bit.64", ".0123", ".pac"):
+        keep = open(pre + ext, "rb").read()
+        with open(pre + ext, "wb") as f:
+            f.write(keep[:-1])
+        assert not bench_legs.index_complete(pre), ext
+        with open(pre + ext, "wb") as f:
+            f.write(keep)
+    assert bench_legs.index_complete(pre)
+    os.remove(pre + ".0123")
+    assert not bench_legs.index_complete(pre)
+    assert bench_legs.n_contigs(str(tmp_path / "none.contigs.npz")) == 0

@@ -43,6 +43,29 @@ def contig_lengths(total_bp):
     return [int(x) for x in l]
 
 
+def index_complete(pre):
+    """the index files of `pre` are there and exactly as long as the .ann / .bwt.2bit.64 headers say (the loader's layout, index_io.cpp): a cached
+    index that was cut short by whatever copied or kept it is built again rather than loaded"""
+    try:
+        with open(pre + ".ann") as f:
+            l_pac = int(f.readline().split()[0])
+        with open(pre + ".bwt.2bit.64", "rb") as f:
+            ref_len = int(np.frombuffer(f.read(8), "<i8")[0])
+        want = {".bwt.2bit.64": 48 + 64 * ((ref_len >> 6) + 1) + 5 * ((ref_len >> 3) + 1) + 8, ".0123": 2 * l_pac, ".pac": (l_pac >> 2) + 2}
+        return ref_len == 2 * l_pac + 1 and os.path.getsize(pre + ".amb") > 0 and all(os.path.getsize(pre + s) == n for s, n in want.items())
+    except (OSError, ValueError, IndexError):
+        return False
+
+
+def n_contigs(meta):
+    """contigs held by the cached .contigs.npz; 0 if it is missing or cut short (a cut zip has lost its central directory: it does not open)"""
+    try:
+        with np.load(meta, allow_pickle=True) as z:
+            return int(z["n"])
+    except Exception:                                             # noqa  (OSError, ValueError, zipfile.BadZipFile, ...)
+        return 0
+
+
 def prepare_genome(workdir, mbp, seed):
     from tools import synth
     pre = os.path.join(workdir, "genome_%dmbp_s%d.fa" % (mbp, seed))
@@ -55,10 +78,22 @@ def prepare_genome(workdir, mbp, seed):
             memo.append([z["c%d" % i] for i in range(int(z["n"]))])
         return memo[0]
     lens_fn = pre + ".contig_lens.npy"                        # (tools/gen_chunk.py samples reads from the mapped .0123 with these)
-    if os.path.exists(pre + ".bwt.2bit.64") and os.path.exists(meta):
-        if not os.path.exists(lens_fn):
+    n_ctg = n_contigs(meta)
+    if index_complete(pre) and n_ctg > 0:
+        try:
+            ok = len(np.load(lens_fn)) == n_ctg
+        except Exception:                                         # noqa
+            ok = False
+        if not ok:
             np.save(lens_fn, np.array([len(c) for c in contigs()], np.int64))
         return pre, contigs
+    if os.path.exists(pre + ".bwt.2bit.64") or os.path.exists(meta):
+        log("cached genome / index in %s incomplete: built again" % workdir)
+        for fn in (meta, lens_fn):
+            try:
+                os.remove(fn)
+            except OSError:
+                pass
     import bm2
     t = time.time()
     total = int(mbp * 1e6)
@@ -84,7 +119,13 @@ def pe_chunk(workdir, contigs_fn, seed, n_reads, read_len, tag=""):
     from tools import synth
     fn = os.path.join(workdir, "chunk_pe_s%d_n%d_l%d%s.npy" % (seed, n_reads, read_len, tag))
     if os.path.exists(fn):
-        return np.load(fn)
+        try:
+            seqs = np.load(fn)
+            if seqs.shape == (2 * (n_reads // 2), read_len):
+                return seqs
+        except (OSError, ValueError, EOFError):
+            pass
+        log("cached chunk %s incomplete: generated again" % fn)
     r1, r2 = synth.make_reads_pe(seed, contigs_fn(), n_reads // 2, L=read_len)
     seqs = np.empty((2 * len(r1), read_len), np.uint8)
     seqs[0::2] = r1; seqs[1::2] = r2
@@ -704,7 +745,7 @@ def side_workload(a, name, extra, limit_s):
         os.remove(full)
     except OSError:
         pass
-    cmd = [sys.executable, BENCH_PY, "--workload", name, "--gpus", "1", "--genome-mbp", str(a.genome_mbp), "--workdir", a.workdir, "--full-json", full,
+    cmd = [sys.executable, BENCH_PY, "--full", "--workload", name, "--gpus", "1", "--genome-mbp", str(a.genome_mbp), "--workdir", a.workdir, "--full-json", full,
            "--no-e2e", "--no-binding", "--no-side-workloads", "--budget-s", str(int(limit_s))] + [str(x) for x in extra]
     t = time.time()
     try:
@@ -788,13 +829,20 @@ def bench_bsw(a, bm2, torch, dist_util, rank, world, local, emu, seed):
         return 0
     steps = max(a.steps, 1)
     k_ms /= steps
-    # parity + CPU baseline: the REFERENCE's own kernels (oracle/_ref/refdump.<isa> bswtime: BandedPairWiseSW::getScores8 / getScores16 /
+    fields = ("score", "qle", "tle", "gtle", "gscore", "max_off")
+    if getattr(a, "dump_outputs", None) and a.steps > 0:        # a fixed, seeded sample of the pairs: their six outputs (float32: exact)
+        sel = np.sort(np.random.default_rng(7919).choice(n, size=min(n, 1 << 20), replace=False))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "pairs.npy"), sel.astype(np.float64))
+        for f in fields:
+            np.save(os.path.join(a.dump_outputs, "bsw_%s.npy" % f), got[f][sel].astype(np.float32))
+        log("outputs of the last step: %d of %d pairs -> %s" % (len(sel), n, a.dump_outputs))
+    # parity + CPU baseline (--full): the REFERENCE's own kernels (oracle/_ref/refdump.<isa> bswtime: BandedPairWiseSW::getScores8 / getScores16 /
     # scalarBandedSWAWrapper, pairs filed and ordered as the reference files and orders them, one BandedPairWiseSW object and one slice per
     # thread) on ALL pairs of the step, on the CPUs this process may use; every pair's six outputs are compared
-    refdump, isa = ref_binary("refdump")
+    refdump, isa = ref_binary("refdump") if a.full else (None, None)
     threads = host_threads()
     cb, par = None, None
-    fields = ("score", "qle", "tle", "gtle", "gscore", "max_off")
     if refdump is not None:
         fn_in, fn_out = os.path.join(a.workdir, "bsw_pairs_r%d.bin" % rank), os.path.join(a.workdir, "bsw_ref_r%d.bin" % rank)
         with open(fn_in, "wb") as f:
@@ -832,7 +880,7 @@ def bench_bsw(a, bm2, torch, dist_util, rank, world, local, emu, seed):
                 os.remove(fn)
             except OSError:
                 pass
-    if par is None:                                              # no compiled reference on this box: the oracle's restatement on a sample, one thread
+    if par is None and a.full:                                   # no compiled reference on this box: the oracle's restatement on a sample, one thread
         n_s = min(n, 3000)
         oopt = oracle.default_opt()
         t = time.time(); bad = 0
@@ -844,7 +892,7 @@ def bench_bsw(a, bm2, torch, dist_util, rank, world, local, emu, seed):
         par = {"pairs": n_s, "sample": "the first %d pairs against the oracle's ksw_extend2 restatement (oracle/_ref is not built here)" % n_s, "pairs_equal": bad == 0, "mismatches": bad}
         cb = {"value": n_s / cpu_s / TASKS_PER_READ if cpu_s > 0 else None, "unit": "reads/s", "cores": 1, "kind": "port",
               "sample": "%d pairs through oracle/bm2_oracle.c (ora_ksw_extend_cls) from Python, one thread, %.1f s" % (n_s, cpu_s)}
-    bad = par["mismatches"]
+    bad = par["mismatches"] if par else 0
     algo_bytes = float(int(roff[-1]) + int(qoff[-1]) + 2 * n * pairs.dtype.itemsize)     # every base once, every SeqPair read and written
     out = {
         "metric": "aligned reads/s (150bp PE vs GRCh38) at 1/2/4/8 GPU; SAM bit-exact vs ref",

@@ -5,7 +5,7 @@
 TAG=${1:-e2e_tl}; Q=${2:-8}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp GPU_MAX_HW_QUEUES=$Q
 T0=$(date +%s)
-timeout 400 rocprofv3 --kernel-trace -d /tmp/p_e2e -o e2e -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-binding > $O/bench.json 2> $O/bench.err; echo "rc=$? at $(( $(date +%s) - T0 ))s"
+timeout 400 rocprofv3 --kernel-trace -d /tmp/p_e2e -o e2e -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-binding > $O/bench.json 2> $O/bench.err; echo "rc=$? at $(( $(date +%s) - T0 ))s"
 python $R/tools/rocpd_timeline.py $(find /tmp/p_e2e -name "*.db" | head -1) $O/timeline.tsv 2>> $O/bench.err
 python - <<P
 import json

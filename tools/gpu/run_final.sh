@@ -15,7 +15,7 @@ grep "\[sweep\]" $O/sweep.err | tail -40
 env | grep "^BM2_" > $O/env_used.txt
 if [ $(left) -gt 70 ]; then
   T=$(( $(left) - 45 )); [ $T -gt 150 ] && T=150
-  timeout $T python bench.py --workload ont2d --steps 3 --warmup 1 --parity-reads 48 > $O/bench_ont2d.json 2> $O/bench_ont2d.err; echo "ont2d rc=$? at $(( $(date +%s) - T0 ))s" | tee -a $O/bench_ont2d.err
+  timeout $T python bench.py --full --workload ont2d --steps 3 --warmup 1 --parity-reads 48 > $O/bench_ont2d.json 2> $O/bench_ont2d.err; echo "ont2d rc=$? at $(( $(date +%s) - T0 ))s" | tee -a $O/bench_ont2d.err
   tail -5 $O/bench_ont2d.err; head -c 700 $O/bench_ont2d.json; echo
 fi
 cd /tmp

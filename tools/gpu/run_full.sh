@@ -9,10 +9,10 @@ export TMPDIR=/tmp
 if [ -z "$SKIP_TESTS" ]; then
   timeout 300 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -4 $O/pytest.log
 fi
-BM2_TAIL_PROF=1 timeout 700 python bench.py --steps $STEPS --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/bench.err; tail -12 $O/bench.err
+BM2_TAIL_PROF=1 timeout 700 python bench.py --full --steps $STEPS --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/bench.err; tail -12 $O/bench.err
 head -c 1500 $O/bench.json; echo
 if [ -z "$SKIP_ONT" ]; then     # config 5 shape on the same index: its own bench line (parity on a sample, CPU baseline on a sample)
-  timeout 500 python bench.py --workload ont2d --steps 3 --warmup 1 --parity-reads 48 > $O/bench_ont2d.json 2> $O/bench_ont2d.err; echo "ont2d rc=$?" >> $O/bench_ont2d.err; tail -6 $O/bench_ont2d.err
+  timeout 500 python bench.py --full --workload ont2d --steps 3 --warmup 1 --parity-reads 48 > $O/bench_ont2d.json 2> $O/bench_ont2d.err; echo "ont2d rc=$?" >> $O/bench_ont2d.err; tail -6 $O/bench_ont2d.err
   head -c 600 $O/bench_ont2d.json; echo
 fi
 if [ -n "$TRY_NSUB" ]; then     # experiment: the chunk as two sub-batches on two sets of streams

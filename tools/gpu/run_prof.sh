@@ -45,7 +45,7 @@ if [ $(left) -gt 50 ]; then      # SQ and TCC counters sit in different blocks: 
 fi
 cd $R
 if [ $(left) -gt 120 ]; then     # the bench as the driver runs it, minus the CPU baseline and the end-to-end leg: the parity gate on the new defaults
-  timeout $(( $(left) - 10 )) python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/bench_parity.json 2> $O/bench_parity.err; echo "bench+parity rc=$? at $(( $(date +%s) - T0 ))s" | tee -a $O/bench_parity.err
+  timeout $(( $(left) - 10 )) python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/bench_parity.json 2> $O/bench_parity.err; echo "bench+parity rc=$? at $(( $(date +%s) - T0 ))s" | tee -a $O/bench_parity.err
   grep "parity" $O/bench_parity.err | tail -4
 fi
 cd /tmp

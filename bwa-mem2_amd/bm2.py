@@ -58,6 +58,21 @@ class SamOpt(C.Structure):
                 ("rescue_inline", C.c_int32), ("rg_id", C.c_char_p)]
 
 
+SAM_F_DEVICE_TEXT = 0x01000000      # BM2_SAM_F_DEVICE_TEXT: sam_*_dev make records and the device formats the text (off by default)
+
+
+class SamRec(C.Structure):          # bm2_samrec_t (include/bm2.h), 128 bytes
+    _fields_ = [("read", C.c_int32), ("flag", C.c_int32), ("rid", C.c_int32), ("mapq", C.c_int32), ("pos", C.c_int64),
+                ("mrid", C.c_int32), ("rnext_eq", C.c_int32), ("mpos", C.c_int64), ("tlen", C.c_int64),
+                ("is_rev", C.c_int32), ("no_seq", C.c_int32), ("qb", C.c_int32), ("qe", C.c_int32),
+                ("cigar_off", C.c_int64), ("n_cigar", C.c_int32), ("n_mc", C.c_int32), ("mc_off", C.c_int64),
+                ("nm", C.c_int32), ("md_len", C.c_int32), ("md_off", C.c_int64), ("score", C.c_int32), ("sub", C.c_int32),
+                ("blob_off", C.c_int64), ("blob_len", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(SamRec) == 128
+
+
 class Fastq(C.Structure):
     _fields_ = [("n_reads", C.c_int32), ("pad", C.c_int32), ("n_bases", C.c_int64), ("enc", C.POINTER(C.c_uint8)),
                 ("off", C.POINTER(C.c_int64)), ("len", C.POINTER(C.c_int32)), ("name", C.POINTER(C.c_char_p)),
@@ -92,7 +107,8 @@ class Stats(C.Structure):
 EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scmat", "bm2_create", "bm2_create_shared", "bm2_destroy",
            "bm2_last_error", "bm2_device_count", "bm2_set_stream_priority", "bm2_host_cpus", "bm2_host_alloc", "bm2_host_free", "bm2_bsw", "bm2_bsw_upload", "bm2_bsw_run", "bm2_bsw_download", "bm2_smem", "bm2_sal", "bm2_seed_chain_extend",
            "bm2_batch_upload", "bm2_batch_run", "bm2_batch_stats", "bm2_batch_download", "bm2_batch_kernel_ms", "bm2_batch_parts",
-           "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats"]
+           "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats",
+           "bm2_sam_format_dev", "bm2_sam_text_stats"]
 
 _lib = None
 
@@ -174,7 +190,9 @@ class Bm2Error(RuntimeError):
 
 def _chk(rc, what):
     if rc != BM2_OK:
-        raise Bm2Error("%s failed (%d): %s" % (what, rc, lib().bm2_last_error().decode()))
+        e = Bm2Error("%s failed (%d): %s" % (what, rc, lib().bm2_last_error().decode()))
+        e.rc = rc
+        raise e
 
 
 def default_opt(**kw):
@@ -458,6 +476,48 @@ class Context:
             _chk(rc, "bm2_sam_pe_dev" if paired else "bm2_sam_se_dev")
             return buf[:need.value]                              # a uint8 view of the buffer the library wrote into (no copy); bytes(x) / x.tobytes() for text
 
+    def sam_format(self, so, enc, off, ln, names, recs, cigar=(), side=b"", quals=None, out=None):
+        """bm2_sam_format_dev: decided records (a sequence of SamRec; offsets into `cigar` / `side`) -> their SAM lines, formatted on
+        the device, as bytes.  out: the caller's uint8 buffer (default: the size is asked for first); when it is too small the Bm2Error
+        carries rc = BM2_ECAP and need = the bytes needed."""
+        L = lib()
+        L.bm2_sam_format_dev.argtypes = [C.c_void_p, C.POINTER(SamOpt), C.POINTER(Reads), C.POINTER(ReadText), C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        r, keep = _reads_struct(enc, off, ln)
+        n = len(keep[2])
+
+        def arr(v):
+            a = (C.c_char_p * max(n, 1))()
+            for i, x in enumerate(v):
+                a[i] = None if x is None else (x if isinstance(x, bytes) else x.encode())
+            return a
+        nm = arr(names)
+        ql = arr(quals) if quals is not None else None
+        t = ReadText(C.cast(nm, C.POINTER(C.c_char_p)), None, C.cast(ql, C.POINTER(C.c_char_p)) if ql is not None else None)
+        ra = (SamRec * max(len(recs), 1))(*recs)
+        cg = np.ascontiguousarray(cigar, np.uint32)
+        sd = np.frombuffer(bytes(side), np.uint8)
+        need = C.c_int64(0)
+
+        def call(buf, cap_):
+            return L.bm2_sam_format_dev(C.c_void_p(self.h), C.byref(so), C.byref(r), C.byref(t), C.c_int64(len(recs)), C.cast(ra, C.c_void_p),
+                                        C.c_void_p(cg.ctypes.data) if len(cg) else None, C.c_int64(len(cg)),
+                                        C.c_void_p(sd.ctypes.data) if len(sd) else None, C.c_int64(len(sd)), buf, C.c_int64(cap_), C.byref(need))
+        if out is None:
+            rc = call(None, 0)
+            if rc not in (0, BM2_ECAP):
+                _chk(rc, "bm2_sam_format_dev")
+            out = np.zeros(max(need.value, 1), np.uint8)
+            cap = need.value
+        else:
+            cap = len(out)
+        rc = call(C.c_void_p(out.ctypes.data), cap)
+        if rc != BM2_OK:
+            e = Bm2Error("bm2_sam_format_dev failed (%d): %s" % (rc, "capacity %d, needed %d" % (cap, need.value) if rc == BM2_ECAP else L.bm2_last_error().decode()))
+            e.rc, e.need = rc, need.value
+            raise e
+        return out[:need.value].tobytes()
+
     def batch_run(self, opt):
         _chk(lib().bm2_batch_run(self.h, C.byref(opt)), "bm2_batch_run")
 
@@ -558,6 +618,16 @@ def sam_cigar_stats():
     """(planned, used, missed) CIGAR alignments of the last sam_se / sam_pe call that ran them as a batch."""
     v = [C.c_int64(0) for _ in range(3)]
     lib().bm2_sam_cigar_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def sam_text_stats():
+    """(records, device_bytes, host_bytes) of the last call that formatted SAM text on the device: lines written, bytes the kernel
+    produced, bytes that arrived pre-formatted."""
+    v = [C.c_int64(0) for _ in range(3)]
+    L = lib()
+    L.bm2_sam_text_stats.restype = None
+    L.bm2_sam_text_stats(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 

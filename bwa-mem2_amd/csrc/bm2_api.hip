@@ -7,6 +7,7 @@
 #include <new>
 #include <mutex>
 #include <algorithm>
+#include <string>
 #include <vector>
 #include "bm2_ctx.h"
 
@@ -433,6 +434,15 @@ extern "C" bm2_ctx *bm2_create(int device, const bm2_index_desc *idx) {
         rc = rc ? rc : upload(&c->d_ann_off, idx->ann_offset, (size_t)idx->n_seqs, c->stream);
         rc = rc ? rc : upload(&c->d_ann_len, idx->ann_len, (size_t)idx->n_seqs, c->stream);
         rc = rc ? rc : upload(&c->d_ann_alt, idx->ann_is_alt, (size_t)idx->n_seqs, c->stream);
+        if (!rc && idx->ann_name && idx->n_seqs > 0) {              // contig names, for the SAM text kernels
+            std::vector<int32_t> noff((size_t)idx->n_seqs + 1, 0);
+            std::string names;
+            for (int i = 0; i < idx->n_seqs; i++) { names += idx->ann_name[i] ? idx->ann_name[i] : ""; noff[(size_t)i + 1] = (int32_t)names.size(); }
+            names.append(64, '\0');
+            rc = upload(&c->d_ann_names, names.data(), names.size(), c->stream);
+            rc = rc ? rc : upload(&c->d_ann_name_off, noff.data(), noff.size(), c->stream);
+            rc = rc ? rc : bm2_check(hipStreamSynchronize(c->stream), "contig names upload");      // (the host copies die here)
+        }
         rc = rc ? rc : bm2_check(hipStreamSynchronize(c->stream), "index upload");
         if (rc) { bm2_destroy(c); return nullptr; }
         DevIndex &ix = c->ix;
@@ -457,6 +467,7 @@ int bm2_ensure_subs(bm2_ctx *c, int n_sub) {
         bm2_ctx *k = new (std::nothrow) bm2_ctx();
         if (!k) break;
         k->device = c->device; k->n_cu = c->n_cu; k->ix = c->ix; k->has_index = true; k->is_child = true; k->is_sub = true;
+        k->d_ann_names = c->d_ann_names; k->d_ann_name_off = c->d_ann_name_off;
         if (make_streams(k)) { delete k; break; }
         c->subs.push_back(k);
     }
@@ -472,6 +483,7 @@ extern "C" bm2_ctx *bm2_create_shared(bm2_ctx *parent) {
     bm2_ctx *k = new (std::nothrow) bm2_ctx();
     if (!k) return nullptr;
     k->device = parent->device; k->n_cu = parent->n_cu; k->ix = parent->ix; k->has_index = parent->has_index; k->is_child = true;
+    k->d_ann_names = parent->d_ann_names; k->d_ann_name_off = parent->d_ann_name_off;
     if (make_streams(k)) { delete k; return nullptr; }
     if (k->has_index) bm2_ensure_subs(k, bm2_knob("BM2_N_SUB", BM2_N_SUB));
     return k;
@@ -506,9 +518,11 @@ extern "C" void bm2_destroy(bm2_ctx *c) {
     }
     c->subs.clear();
     bm2_batch_destroy(c);
-    void *ps[] = { c->d_cp_occ, c->d_sa_ms, c->d_sa_ls, c->d_ref, c->d_ann_off, c->d_ann_len, c->d_ann_alt };
+    void *ps[] = { c->d_cp_occ, c->d_sa_ms, c->d_sa_ls, c->d_ref, c->d_ann_off, c->d_ann_len, c->d_ann_alt, c->d_ann_names, c->d_ann_name_off };
     if (!c->is_child) for (void *p : ps) if (p) (void)hipFree(p);          // a shared context does not own the replica
     bm2_release(c->b_pairs); bm2_release(c->b_pairs2); bm2_release(c->b_ref); bm2_release(c->b_qer); bm2_release(c->b_misc); bm2_release(c->b_scan);
+    bm2_release(c->b_txt_in); bm2_release(c->b_txt_pos); bm2_release(c->b_txt_out); bm2_release(c->b_txt_enc); bm2_release(c->b_txt_scan);
+    if (c->txt_pin) (void)hipHostFree(c->txt_pin);
     free_streams(c);
     delete c;
 }

@@ -34,6 +34,13 @@ struct bm2_ctx {
     // device copies of the index arrays (owned)
     void *d_cp_occ = nullptr, *d_sa_ms = nullptr, *d_sa_ls = nullptr, *d_ref = nullptr;
     void *d_ann_off = nullptr, *d_ann_len = nullptr, *d_ann_alt = nullptr;
+    // contig names for the SAM text kernels (samfmt.hip): the names back to back and n_seqs + 1 offsets; NULL when the descriptor had none
+    void *d_ann_names = nullptr, *d_ann_name_off = nullptr;
+    // workspaces of bm2_sam_format_dev: inputs (records, ops, side bytes, packed names / qualities), sizes and offsets, the text
+    DevBuf b_txt_in, b_txt_pos, b_txt_out, b_txt_enc, b_txt_scan;
+    void *txt_pin = nullptr; size_t txt_pin_cap = 0;              // page-locked staging of the packed names / qualities
+    // the host array whose copy b_ref holds since the CIGAR batch of the SAM tail call in progress (NULL: none); the text of the same call reads it there
+    const void *tail_enc = nullptr; size_t tail_enc_bytes = 0;
     // scratch for the S1/S2 entry points
     DevBuf b_pairs, b_pairs2, b_ref, b_qer, b_misc;
     int n_bsw = 0;                 // pairs of the resident S1 batch (bm2_bsw_upload)

@@ -590,6 +590,7 @@ int bm2_dev_cigar_batch(void *user, const bm2_opt *opt, const bm2_reads *reads, 
     std::vector<CigarRes> &res = res_tl;
     const int rc = cigar_run(c, opt, tasks, reads->enc, enc_bytes, res, out->cigar_off, out->md_off, out->cigar, out->md);
     if (rc) return rc;
+    c->tail_enc = reads->enc; c->tail_enc_bytes = (size_t)enc_bytes;       // (b_ref holds the reads' codes now: the text of the same call reads them there)
     out->score.resize((size_t)n); out->nm.resize((size_t)n); out->n_cigar.resize((size_t)n);
     bm2_parallel_ranges(n, 16384, host_threads, [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) { out->score[(size_t)i] = res[(size_t)i].score; out->nm[(size_t)i] = res[(size_t)i].nm; out->n_cigar[(size_t)i] = res[(size_t)i].n_cigar; }
@@ -601,5 +602,6 @@ extern "C" int bm2_sam_se_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
                               const bm2_read_text *txt, bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, char *out,
                               int64_t cap, int64_t *n_out) {
     if (!c || !c->has_index || !c->ix.ref_string) { bm2_set_error("bm2_sam_se_dev: the context holds no index"); return BM2_EINVAL; }
+    bm2h_text_scope text(&c, 1);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, bm2_dev_cigar_batch, c);
 }

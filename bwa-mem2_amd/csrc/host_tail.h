@@ -24,6 +24,28 @@ struct bm2h_cg_out {
 };
 typedef int (*bm2h_cigar_batch_fn)(void *user, const bm2_opt *opt, const bm2_reads *reads, int64_t enc_bytes, int32_t n, const bm2h_cg_hit *hits,
                                    bm2h_cg_out *out);
+// The text of one chunk from its decided records (bm2_sam_format_dev's arguments after the context; offsets of the records index
+// `cigar` / `side`).  Set through bm2h_text_hook for the calling thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_TEXT the last
+// pass of bm2h_sam_pe / bm2h_sam_se appends records instead of text and hands them to the hook in one call.  The host-only entry
+// points never set it.  0 = success.
+typedef int (*bm2h_text_batch_fn)(void *user, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt, int64_t n_rec,
+                                  const bm2_samrec_t *recs, const uint32_t *cigar, int64_t n_cigar, const char *side, int64_t side_bytes,
+                                  char *out, int64_t cap, int64_t *n_out);
+struct bm2h_text_hook {             // scoped: the hook of the calling thread for the bm2h_sam_* call made inside the scope
+    bm2h_text_hook(bm2h_text_batch_fn fn, void *user);
+    ~bm2h_text_hook();
+};
+// The device's hook (samfmt.hip) and the scope the _dev entry points open around their bm2h_sam_* call: the hook over their context(s), and
+// no context believing that it still holds the reads of an earlier call.
+struct bm2_ctx;
+struct bm2h_text_ctxs { bm2_ctx *const *ctx; int n; };
+int bm2h_dev_text_batch(void *user, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt, int64_t n_rec, const bm2_samrec_t *recs,
+                        const uint32_t *cigar, int64_t n_cigar, const char *side, int64_t side_bytes, char *out, int64_t cap, int64_t *n_out);
+struct bm2h_text_scope {
+    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_text_hook hook;
+    bm2h_text_scope(bm2_ctx *const *ctx, int n);
+    ~bm2h_text_scope();
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -343,6 +343,18 @@ thread_local long long t_cg_used = 0, t_cg_missed = 0, t_rs_used = 0, t_rs_misse
 struct CgSession { int mode = 0; std::vector<int32_t> *rec = nullptr; const CgMemo *memo = nullptr; CgStats *st = nullptr; };   // mode 1 = record, 2 = replay
 thread_local CgSession t_cg;
 
+// ---- the record sink of the device-text path (BM2_SAM_F_DEVICE_TEXT): aln2sam appends one bm2_samrec_t, the line's CIGAR ops (its own and
+// the mate's for MC:Z:, S or H chosen), its MD bytes and its pre-formatted tail to the thread's buffers instead of formatting.  Offsets are
+// relative to the thread's buffers; run_blocks moves them to the chunk's when it copies the blocks to their places.
+struct RecSink {
+    std::vector<bm2_samrec_t> recs; std::vector<uint32_t> cg; Text side;
+    void clear() { recs.clear(); cg.clear(); side.clear(); }
+};
+thread_local RecSink *t_rec = nullptr;                          // set while a thread runs the real pass with records as its output
+thread_local int t_rec_base = 0, t_rec_read = 0;                                // first read of the pair / the read whose lines are being made (the callers of aln2sam say)
+thread_local bm2h_text_batch_fn t_text_fn = nullptr;            // the calling thread's hook (bm2h_text_hook)
+thread_local void *t_text_user = nullptr;
+
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
 int reg2aln_band(const bm2_opt *opt, int qb, int qe, int64_t rb, int64_t re, int truesc, int w_hit) {
     const int tmp = infer_bw(qe - qb, (int)(re - rb), truesc, opt->a, opt->o_del, opt->e_del);
@@ -594,14 +606,76 @@ void aln2sam(const bm2_sam_opt *so, const Ref &R, Text &s, const char *name, con
     if (has_mate && m_rid < 0 && p_rid >= 0) { m_rid = p_rid; m_pos = p_pos; m_rev = p_rev; m_cg = &no_cigar; }         // copy alignment to mate
     p_flag |= p_rev ? 0x10 : 0;
     p_flag |= has_mate && m_rev ? 0x20 : 0;
-    auto put_cigar_of = [&](const AVec<uint32_t> &cg, int is_alt) {     // add_cigar, bwamem.cpp:1579-1590
+    auto clip_op = [&](uint32_t c0, int is_alt) {                       // add_cigar, bwamem.cpp:1579-1590: S or H for a clip
+        int c = c0 & 0xf;
+        if (!(so->flag & F_SOFTCLIP) && !is_alt && (c == 3 || c == 4)) c = which ? 4 : 3;
+        return c;
+    };
+    auto put_cigar_of = [&](const AVec<uint32_t> &cg, int is_alt) {
         if (cg.empty()) { s.push_back('*'); return; }
-        for (uint32_t c0 : cg) {
-            int c = c0 & 0xf;
-            if (!(so->flag & F_SOFTCLIP) && !is_alt && (c == 3 || c == 4)) c = which ? 4 : 3;
-            put_int(s, c0 >> 4); s.push_back("MIDSH"[c]);
+        for (uint32_t c0 : cg) { put_int(s, c0 >> 4); s.push_back("MIDSH"[clip_op(c0, is_alt)]); }
+    };
+    int64_t tlen = 0;                                            // template length: only for two placed ends on one contig
+    if (has_mate && m_rid >= 0 && p_rid == m_rid && !m_cg->empty() && !p_cg->empty()) {
+        const int64_t p0 = p_pos + (p_rev ? get_rlen(*p_cg) - 1 : 0), p1 = m_pos + (m_rev ? get_rlen(*m_cg) - 1 : 0);
+        tlen = -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0));
+    }
+    int qb = 0, qe = l_seq;                                      // the stretch of the read SEQ / QUAL print: hard clips shorten it
+    if (!(p_flag & 0x100) && !p_cg->empty() && which && !(so->flag & F_SOFTCLIP) && !P.is_alt) {
+        const uint32_t c0 = (*p_cg)[0], c1 = p_cg->back();
+        if (!p_rev) {
+            if ((c0 & 0xf) == 4 || (c0 & 0xf) == 3) qb += c0 >> 4;
+            if ((c1 & 0xf) == 4 || (c1 & 0xf) == 3) qe -= c1 >> 4;
+        } else {
+            if ((c0 & 0xf) == 4 || (c0 & 0xf) == 3) qe -= c0 >> 4;
+            if ((c1 & 0xf) == 4 || (c1 & 0xf) == 3) qb += c1 >> 4;
+        }
+    }
+    auto put_tail = [&](Text &t) {                               // what follows RG:Z: (bwamem.cpp:1696-1727): SA, pa, XA, the comment, XR
+        if (!(p_flag & 0x100)) {
+            int i;
+            for (i = 0; i < n; ++i) if (i != which && !(list[i].flag & 0x100)) break;
+            if (i < n) {
+                t += "\tSA:Z:";
+                for (i = 0; i < n; ++i) {
+                    const Aln &r = list[i];
+                    if (i == which || (r.flag & 0x100)) continue;
+                    t += R.name[r.rid]; t.push_back(','); put_int(t, r.pos + 1); t.push_back(','); t.push_back("+-"[r.is_rev]); t.push_back(',');
+                    put_cigar(t, r.cigar, "MIDSH");
+                    t.push_back(','); put_int(t, r.mapq); t.push_back(','); put_int(t, r.NM); t.push_back(';');
+                }
+            }
+            if (P.alt_sc > 0) { char b[64]; snprintf(b, sizeof b, "\tpa:f:%.3f", (double)P.score / P.alt_sc); t += b; }
+        }
+        if (P.XA) { t += "\tXA:Z:"; t.append(P.XA->p, (size_t)P.XA->n); }
+        if (comment) { t.push_back('\t'); t += comment; }
+        if ((so->flag & F_REF_HDR) && p_rid >= 0 && R.anno && R.anno[p_rid] && R.anno[p_rid][0]) {
+            t += "\tXR:Z:";
+            for (const char *c = R.anno[p_rid]; *c; ++c) t.push_back(*c == '\t' ? ' ' : *c);
         }
     };
+    if (t_rec) {                                                 // device text: the decided record, with copies of what is gone with the next pair
+        RecSink &K = *t_rec;
+        bm2_samrec_t r; memset(&r, 0, sizeof r);
+        r.read = t_rec_read; r.flag = (p_flag & 0xffff) | (p_flag & 0x10000 ? 0x100 : 0);
+        r.rid = p_rid; r.mapq = P.mapq; r.pos = p_pos + 1;
+        const bool mate_placed = has_mate && m_rid >= 0;
+        r.mrid = mate_placed ? m_rid : -1; r.rnext_eq = mate_placed && p_rid == m_rid; r.mpos = m_pos + 1; r.tlen = tlen;
+        r.is_rev = p_rev; r.no_seq = (p_flag & 0x100) != 0; r.qb = qb; r.qe = qe > qb ? qe : qb;
+        r.cigar_off = (int64_t)K.cg.size(); r.n_cigar = p_rid >= 0 ? p_cg->size() : 0;
+        for (int k = 0; k < r.n_cigar; ++k) { const uint32_t c0 = (*p_cg)[k]; K.cg.push_back((c0 & ~0xfu) | (uint32_t)clip_op(c0, P.is_alt)); }
+        r.mc_off = (int64_t)K.cg.size(); r.n_mc = has_mate ? m_cg->size() : 0;
+        for (int k = 0; k < r.n_mc; ++k) { const uint32_t c0 = (*m_cg)[k]; K.cg.push_back((c0 & ~0xfu) | (uint32_t)clip_op(c0, m_->is_alt)); }
+        r.nm = P.NM; r.md_off = (int64_t)K.side.size();
+        if (!p_cg->empty()) K.side += P.MD;
+        r.md_len = (int32_t)((int64_t)K.side.size() - r.md_off);
+        r.score = P.score; r.sub = P.sub;
+        r.blob_off = (int64_t)K.side.size();
+        put_tail(K.side);
+        r.blob_len = (int32_t)((int64_t)K.side.size() - r.blob_off);
+        K.recs.push_back(r);
+        return;
+    }
     s += name; s.push_back('\t');
     put_int(s, (p_flag & 0xffff) | (p_flag & 0x10000 ? 0x100 : 0)); s.push_back('\t');
     if (p_rid >= 0) {
@@ -615,26 +689,11 @@ void aln2sam(const bm2_sam_opt *so, const Ref &R, Text &s, const char *name, con
         if (p_rid == m_rid) s.push_back('='); else s += R.name[m_rid];
         s.push_back('\t');
         put_int(s, m_pos + 1); s.push_back('\t');
-        if (p_rid == m_rid) {
-            const int64_t p0 = p_pos + (p_rev ? get_rlen(*p_cg) - 1 : 0), p1 = m_pos + (m_rev ? get_rlen(*m_cg) - 1 : 0);
-            if (m_cg->empty() || p_cg->empty()) s.push_back('0');
-            else put_int(s, -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
-        } else s.push_back('0');
+        put_int(s, tlen);
     } else s += "*\t0\t0";
     s.push_back('\t');
     if (p_flag & 0x100) s += "*\t*";
     else {
-        int qb = 0, qe = l_seq;
-        if (!p_cg->empty() && which && !(so->flag & F_SOFTCLIP) && !P.is_alt) {
-            const uint32_t c0 = (*p_cg)[0], c1 = p_cg->back();
-            if (!p_rev) {
-                if ((c0 & 0xf) == 4 || (c0 & 0xf) == 3) qb += c0 >> 4;
-                if ((c1 & 0xf) == 4 || (c1 & 0xf) == 3) qe -= c1 >> 4;
-            } else {
-                if ((c0 & 0xf) == 4 || (c0 & 0xf) == 3) qe -= c0 >> 4;
-                if ((c1 & 0xf) == 4 || (c1 & 0xf) == 3) qb += c1 >> 4;
-            }
-        }
         const size_t len = qe > qb ? (size_t)(qe - qb) : 0;
         char *d = s.extend(len + 1 + (qual ? len : 1));          // bases, tab, qualities (or '*') written in place
         if (!p_rev) {
@@ -652,27 +711,7 @@ void aln2sam(const bm2_sam_opt *so, const Ref &R, Text &s, const char *name, con
     if (P.score >= 0) { s += "\tAS:i:"; put_int(s, P.score); }
     if (P.sub >= 0) { s += "\tXS:i:"; put_int(s, P.sub); }
     if (so->rg_id && so->rg_id[0]) { s += "\tRG:Z:"; s += so->rg_id; }
-    if (!(p_flag & 0x100)) {
-        int i;
-        for (i = 0; i < n; ++i) if (i != which && !(list[i].flag & 0x100)) break;
-        if (i < n) {
-            s += "\tSA:Z:";
-            for (i = 0; i < n; ++i) {
-                const Aln &r = list[i];
-                if (i == which || (r.flag & 0x100)) continue;
-                s += R.name[r.rid]; s.push_back(','); put_int(s, r.pos + 1); s.push_back(','); s.push_back("+-"[r.is_rev]); s.push_back(',');
-                put_cigar(s, r.cigar, "MIDSH");
-                s.push_back(','); put_int(s, r.mapq); s.push_back(','); put_int(s, r.NM); s.push_back(';');
-            }
-        }
-        if (P.alt_sc > 0) { char b[64]; snprintf(b, sizeof b, "\tpa:f:%.3f", (double)P.score / P.alt_sc); s += b; }
-    }
-    if (P.XA) { s += "\tXA:Z:"; s.append(P.XA->p, (size_t)P.XA->n); }
-    if (comment) { s.push_back('\t'); s += comment; }
-    if ((so->flag & F_REF_HDR) && p_rid >= 0 && R.anno && R.anno[p_rid] && R.anno[p_rid][0]) {
-        s += "\tXR:Z:";
-        for (const char *c = R.anno[p_rid]; *c; ++c) s.push_back(*c == '\t' ? ' ' : *c);
-    }
+    put_tail(s);
     s.push_back('\n');
 }
 
@@ -1346,7 +1385,9 @@ bool pe_emit(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const PeSt
                 aa[i].push_back(g);
             }
         }
+        t_rec_read = t_rec_base;
         for (int i = 0; i < (int)aa[0].size(); ++i) aln2sam(so, R, out, s[0].name, s[0].comment, s[0].qual, s[0].l_seq, s[0].seq, aa[0], i, &h[1]);
+        t_rec_read = t_rec_base + 1;
         for (int i = 0; i < (int)aa[1].size(); ++i) aln2sam(so, R, out, s[1].name, s[1].comment, s[1].qual, s[1].l_seq, s[1].seq, aa[1], i, &h[0]);
         return true;
     }
@@ -1364,7 +1405,9 @@ bool pe_emit(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const PeSt
         const int d = infer_dir(R.l_pac, a[0][0].rb, a[1][0].rb, &dist);
         if (!pes[d].failed && dist >= pes[d].low && dist <= pes[d].high) extra_flag |= 2;
     }
+    t_rec_read = t_rec_base;
     if (!reg2sam(opt, so, R, out, s[0].name, s[0].comment, s[0].qual, s[0].l_seq, s[0].seq, (int)a[0].size(), a[0].data(), 0x41 | extra_flag, &h[1])) return false;
+    t_rec_read = t_rec_base + 1;
     if (!reg2sam(opt, so, R, out, s[1].name, s[1].comment, s[1].qual, s[1].l_seq, s[1].seq, (int)a[1].size(), a[1].data(), 0x81 | extra_flag, &h[0])) return false;
     return true;
 }
@@ -1439,7 +1482,11 @@ inline void cpu_relax() {
 // *n_out = bytes needed; BM2_ECAP when cap is smaller (nothing useful was written); a failing item makes the call return BM2_EINVAL with the
 // item's number in `bad`.
 struct BlockNote { int block; size_t at, size; };
-template <class F> int run_blocks(int n, int n_threads, char *out, int64_t cap, int64_t *n_out, int *bad, F f) {
+template <class F> int run_blocks_records(int n, int n_threads, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
+                                          char *out, int64_t cap, int64_t *n_out, int *bad, F f);
+template <class F> int run_blocks(int n, int n_threads, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
+                                  char *out, int64_t cap, int64_t *n_out, int *bad, F f) {
+    if (so->flag & BM2_SAM_F_DEVICE_TEXT) return run_blocks_records(n, n_threads, so, reads, txt, out, cap, n_out, bad, f);
     if (n_threads <= 0) n_threads = bm2_effective_cpus();
     if (n_threads < 1) n_threads = 1;
     const int block = 256;
@@ -1485,7 +1532,82 @@ template <class F> int run_blocks(int n, int n_threads, char *out, int64_t cap, 
     return BM2_OK;
 }
 
+// The same walk with RECORDS as the threads' output (BM2_SAM_F_DEVICE_TEXT): every thread appends the records, CIGAR ops and side bytes of
+// the blocks it draws to its own buffers; the blocks' places in the chunk's three arrays are prefix sums over the blocks; every thread
+// copies its blocks there, moving the records' offsets from thread-relative to chunk-relative on the way (the copy is the only pass over
+// the records); the calling thread's hook turns the arrays into text.
+struct RecNote { int block; size_t rec_at, n_rec, cg_at, n_cg, side_at, n_side; };
+struct RecChunk { std::vector<bm2_samrec_t> recs; std::vector<uint32_t> cg; std::vector<char> side; };
+template <class F> int run_blocks_records(int n, int n_threads, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
+                                          char *out, int64_t cap, int64_t *n_out, int *bad, F f) {
+    const bm2h_text_batch_fn tfn = t_text_fn; void *const tuser = t_text_user;
+    if (n_threads <= 0) n_threads = bm2_effective_cpus();
+    if (n_threads < 1) n_threads = 1;
+    const int block = 256;
+    const int n_blocks = (n + block - 1) / block;
+    if (n_threads > n_blocks) n_threads = n_blocks > 0 ? n_blocks : 1;
+    std::vector<int64_t> rec_of((size_t)n_blocks + 1, 0), cg_of((size_t)n_blocks + 1, 0), side_of((size_t)n_blocks + 1, 0);   // sizes, then offsets
+    std::atomic<int> next(0), failed(-1);
+    TailProf prof("run_blocks");
+    static thread_local RecSink sink;                            // (a worker thread's own, kept from chunk to chunk)
+    static thread_local std::vector<RecNote> notes;
+    static thread_local Text unused;
+    run_threads(n_threads, [&]() {
+        sink.clear(); notes.clear();
+        t_rec = &sink;
+        for (;;) {
+            const int b = next.fetch_add(1);
+            if (b >= n_blocks) break;
+            const size_t r0 = sink.recs.size(), c0 = sink.cg.size(), s0 = sink.side.size();
+            if (failed.load(std::memory_order_relaxed) < 0) {
+                const int hi = (b + 1) * block < n ? (b + 1) * block : n;
+                for (int i = b * block; i < hi; ++i)
+                    if (!f(i, unused)) { int e = -1; failed.compare_exchange_strong(e, i); break; }
+            }
+            notes.push_back({ b, r0, sink.recs.size() - r0, c0, sink.cg.size() - c0, s0, sink.side.size() - s0 });
+            rec_of[(size_t)b + 1] = (int64_t)(sink.recs.size() - r0); cg_of[(size_t)b + 1] = (int64_t)(sink.cg.size() - c0);
+            side_of[(size_t)b + 1] = (int64_t)(sink.side.size() - s0);
+        }
+        t_rec = nullptr;
+        flush_tallies();
+    });
+    prof.mark("records");
+    if (failed.load() >= 0) { *bad = failed.load(); *n_out = 0; return BM2_EINVAL; }
+    for (int b = 0; b < n_blocks; ++b) {
+        rec_of[(size_t)b + 1] += rec_of[(size_t)b]; cg_of[(size_t)b + 1] += cg_of[(size_t)b]; side_of[(size_t)b + 1] += side_of[(size_t)b];
+    }
+    static thread_local RecChunk chunk_of_this_thread;           // (the calling thread's, kept from chunk to chunk)
+    RecChunk &C = chunk_of_this_thread;
+    const size_t n_rec = (size_t)rec_of[(size_t)n_blocks], n_cg = (size_t)cg_of[(size_t)n_blocks], n_side = (size_t)side_of[(size_t)n_blocks];
+    if (C.recs.size() < n_rec + 1) C.recs.resize(n_rec + 1);
+    if (C.cg.size() < n_cg + 1) C.cg.resize(n_cg + 1);
+    if (C.side.size() < n_side + 1) C.side.resize(n_side + 1);
+    const size_t RETAIN = (size_t)64 << 20;
+    run_threads(n_threads, [&]() {
+        for (const RecNote &k : notes) {
+            const int64_t dc = cg_of[(size_t)k.block] - (int64_t)k.cg_at, ds = side_of[(size_t)k.block] - (int64_t)k.side_at;
+            bm2_samrec_t *dst = C.recs.data() + rec_of[(size_t)k.block];
+            for (size_t i = 0; i < k.n_rec; ++i) {
+                bm2_samrec_t r = sink.recs[k.rec_at + i];
+                r.cigar_off += dc; r.mc_off += dc; r.md_off += ds; r.blob_off += ds;
+                dst[i] = r;
+            }
+            if (k.n_cg) memcpy(C.cg.data() + cg_of[(size_t)k.block], sink.cg.data() + k.cg_at, k.n_cg * sizeof(uint32_t));
+            if (k.n_side) memcpy(C.side.data() + side_of[(size_t)k.block], sink.side.data() + k.side_at, k.n_side);
+        }
+        notes.clear();
+        if (sink.side.capacity() > RETAIN) sink.side.release();
+    });
+    prof.mark("gather");
+    const int rc = tfn(tuser, so, reads, txt, (int64_t)n_rec, C.recs.data(), C.cg.data(), (int64_t)n_cg, C.side.data(), (int64_t)n_side, out, cap, n_out);
+    prof.mark("device text");
+    return rc;
+}
+
 }  // namespace
+
+bm2h_text_hook::bm2h_text_hook(bm2h_text_batch_fn fn, void *user) { t_text_fn = fn; t_text_user = user; }
+bm2h_text_hook::~bm2h_text_hook() { t_text_fn = nullptr; t_text_user = nullptr; }
 
 extern "C" void bm2_sam_opt_init(bm2_sam_opt *o) {
     if (!o) return;
@@ -1620,6 +1742,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (!idx || !opt || !so || !reads || !txt || !txt->name || !reg_off || !n_out || (reads->n_reads & 1) || (!alnregs && reg_off[reads->n_reads] > 0)) {
         bm2_set_error("bm2_sam_pe: bad argument (reads must be interleaved pairs)"); return BM2_EINVAL;
     }
+    if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
     if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_sam_pe: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
@@ -1800,6 +1923,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     auto emit = [&](int pi, const PairPlan &P, Text &part) {
         ReadIO io[2]; io_of(pi, io);
         t_scratch.reset();                                       // (the pair's CIGARs, XA strings and record lists: gone with the next pair)
+        t_rec_base = 2 * pi;
         return pe_emit(opt, so, R, pes, io, lists + 2 * pi, P, part);
     };
     static thread_local CgMemo memo_of_this_thread;              // (kept from chunk to chunk, like W)
@@ -1836,7 +1960,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         prof.mark("cigar session");
     }
     int bad = -1;
-    const int rc_out = run_blocks(n_pairs, so->n_threads, out, cap, n_out, &bad, [&](int pi, Text &part) {
+    const int rc_out = run_blocks(n_pairs, so->n_threads, so, reads, txt, out, cap, n_out, &bad, [&](int pi, Text &part) {
         if (!cfn) { PairPlan P; decide(pi, P); return emit(pi, P, part); }
         t_cg.mode = 2; t_cg.memo = &memo; t_cg.st = &g_cigar;
         const bool r = emit(pi, plans[(size_t)pi], part);
@@ -1862,6 +1986,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (!idx || !opt || !so || !reads || !txt || !txt->name || !reg_off || !n_out || (!alnregs && reg_off[reads->n_reads] > 0)) {
         bm2_set_error("bm2_sam_se: bad argument"); return BM2_EINVAL;
     }
+    if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);
@@ -1876,6 +2001,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     };
     auto emit = [&](int i, Text &part) {                         // reads the list only: a CIGAR session runs it twice
         t_scratch.reset();
+        t_rec_read = i;
         return reg2sam(opt, so, R, part, txt->name[i], txt->comment ? txt->comment[i] : 0, txt->qual ? txt->qual[i] : 0, reads->len[i],
                        reads->enc + reads->off[i], (int)(reg_off[i + 1] - reg_off[i]), alnregs + reg_off[i], 0, 0);
     };
@@ -1906,7 +2032,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         if (rc) return rc;
     }
     int bad = -1;
-    const int rc_out = run_blocks(n_reads, so->n_threads, out, cap, n_out, &bad, [&](int i, Text &part) {
+    const int rc_out = run_blocks(n_reads, so->n_threads, so, reads, txt, out, cap, n_out, &bad, [&](int i, Text &part) {
         if (!cfn) { decide(i); return emit(i, part); }
         t_cg.mode = 2; t_cg.memo = &memo; t_cg.st = &g_cigar;
         const bool r = emit(i, part);

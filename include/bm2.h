@@ -318,6 +318,52 @@ int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_index_desc *
                          const bm2_read_text *txt, const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed,
                          const bm2_pestat *pes_in, bm2_pestat *pes_out, char *out, int64_t cap, int64_t *n_out);
 
+/* ---- SAM text on the device (samfmt.hip): mem_aln2sam (bwamem.cpp:1592-1730) for a batch of records whose fields are all DECIDED.
+ * bm2_samrec_t is what mem_aln2sam holds in its locals once the mate copies and the flags are through: no host pointers, every
+ * variable-length piece with its length, so that the device sizes a line without scanning a string. */
+typedef struct {
+    int32_t read;                   /* index into reads / txt: QNAME, SEQ, QUAL */
+    int32_t flag;                   /* FLAG as printed */
+    int32_t rid;                    /* contig of RNAME; < 0: the `*\t0\t0\t*` form (pos, mapq, CIGAR not printed) */
+    int32_t mapq;
+    int64_t pos;                    /* POS as printed (1-based) */
+    int32_t mrid;                   /* contig of RNEXT; < 0: no mate position, `*\t0\t0` */
+    int32_t rnext_eq;               /* != 0: RNEXT prints `=` */
+    int64_t mpos;                   /* PNEXT as printed */
+    int64_t tlen;                   /* TLEN as printed */
+    int32_t is_rev;                 /* != 0: SEQ reverse-complemented, QUAL reversed */
+    int32_t no_seq;                 /* != 0: SEQ and QUAL print `*\t*` (flag 0x100) */
+    int32_t qb, qe;                 /* the stretch [qb, qe) of the read SEQ / QUAL print (hard clips of supplementary lines), read coordinates */
+    int64_t cigar_off;              /* ops of this line in `cigar` (S or H already chosen); n_cigar == 0 prints `*` and no NM / MD */
+    int32_t n_cigar;
+    int32_t n_mc;                   /* ops of the mate's CIGAR (MC:Z:) at mc_off; 0: no MC tag */
+    int64_t mc_off;
+    int32_t nm;                     /* NM:i: */
+    int32_t md_len;                 /* bytes of the MD:Z: value at side[md_off] */
+    int64_t md_off;
+    int32_t score, sub;             /* AS:i: / XS:i:; negative: not printed */
+    int64_t blob_off;               /* pre-formatted bytes appended verbatim before the newline (SA:Z:, pa:f:, XA:Z:, the -C comment, */
+    int32_t blob_len;               /* XR:Z:, each with its leading tab), at side[blob_off] */
+    int32_t pad;
+} bm2_samrec_t;                     /* 128 B */
+#ifdef __cplusplus
+static_assert(sizeof(bm2_samrec_t) == 128, "bm2_samrec_t is 128 bytes (mirrored by bm2.py)");
+#endif
+/* n_rec records -> their SAM lines, in order, formatted by k_sam_size / k_sam_write.  cigar: BAM-encoded ops (len << 4 | index into
+ * "MIDSH"); side: MD strings and blobs.  Contig names come from the context (uploaded by bm2_create; BM2_EINVAL when its descriptor
+ * had none), RG:Z: from so->rg_id, names / qualities from txt, bases from reads.  *n_out = bytes needed; BM2_ECAP when cap is
+ * smaller, and then nothing has been written to `out`. */
+int bm2_sam_format_dev(bm2_ctx *c, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
+                       int64_t n_rec, const bm2_samrec_t *recs, const uint32_t *cigar, int64_t n_cigar,
+                       const char *side, int64_t side_bytes, char *out, int64_t cap, int64_t *n_out);
+/* A library-private bit of bm2_sam_opt.flag (outside the reference's MEM_F_* range): bm2_sam_se_dev / bm2_sam_pe_dev and their _multi
+ * forms make records instead of text in their last pass and take the text from bm2_sam_format_dev on the same context(s).  Same
+ * bytes.  Off by default.  bm2_sam_se / bm2_sam_pe have no context and answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_TEXT 0x01000000
+/* Counters of the last call on this process that formatted on the device: lines written, bytes the kernel produced, bytes that
+ * arrived pre-formatted (the blobs). */
+void bm2_sam_text_stats(int64_t *records, int64_t *device_bytes, int64_t *host_bytes);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

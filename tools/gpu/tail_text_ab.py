@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""SAM text on the host against SAM text on the device (BM2_SAM_F_DEVICE_TEXT), on ONE chunk with nothing else running: the device
+produces the hits of a paired chunk once (the bench's cached genome), then bm2_sam_pe_dev runs on it with the bit off and on, ALTERNATING
+in one process -- two warm-up calls each, then --calls timed calls each, the two texts compared every time.  Per variant: median and
+spread of wall ms and of process CPU-s per call (resource.getrusage), the phases BM2_TAIL_PROF=1 prints (medians), the counters of
+bm2_sam_text_stats and the bytes that cross PCIe each way, counted from the chunk.  --parent-lib: a second process of this tool loads
+that library (the parent commit's build) and times its bit-off path on the same chunk first: the baseline for "CPU-s per chunk".
+    python tools/gpu/tail_text_ab.py --out profiles/sam_text_dev_ab.json [--parent-lib PATH] [--pairs 500000] [--genome-mbp 3100] [--calls 10]
+--once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
+import argparse
+import json
+import os
+import re
+import resource
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "bwa-mem2_amd"))
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+os.environ.setdefault("BM2_MALLOC_TUNE", "1")
+
+
+def cpu_s():
+    r = resource.getrusage(resource.RUSAGE_SELF)
+    return r.ru_utime + r.ru_stime
+
+
+class Stderr:
+    """fd 2 into a file while the library prints its phases"""
+
+    def __enter__(self):
+        self.f = tempfile.TemporaryFile()
+        sys.stderr.flush()
+        self.saved = os.dup(2)
+        os.dup2(self.f.fileno(), 2)
+        return self
+
+    def __exit__(self, *a):
+        os.dup2(self.saved, 2)
+        os.close(self.saved)
+        self.f.seek(0)
+        self.text = self.f.read().decode(errors="replace")
+        self.f.close()
+
+
+def phases(text):
+    out = {}
+    for m in re.finditer(r"\[tail\] (\S+)\s+(.+?)\s+([0-9.]+) ms", text):
+        out.setdefault("%s: %s" % (m.group(1), m.group(2).strip()), []).append(float(m.group(3)))
+    return {k: sum(v) for k, v in out.items()}
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median": float(np.median(v)), "min": v[0], "max": v[-1], "n": len(v)}
+
+
+def pcie_ledger(text, n_reads, name_bytes, host_blob):
+    """bytes the device-text path moves, counted from the chunk's text: 128 B a record + 32 B of per-record offsets, 4 B an op (the line's
+    CIGAR and MC:Z:), the MD strings and the blobs, the names and the printed qualities up; the text down."""
+    n_rec = ops = md = qual = 0
+    op = re.compile(rb"[MIDSH]")
+    for line in text.split(b"\n"):
+        if not line:
+            continue
+        f = line.split(b"\t")
+        n_rec += 1
+        if f[5] != b"*":
+            ops += len(op.findall(f[5]))
+        if f[10] != b"*":
+            qual += len(f[10])
+        for t in f[11:]:
+            if t.startswith(b"MD:Z:"):
+                md += len(t) - 5
+            elif t.startswith(b"MC:Z:"):
+                ops += len(op.findall(t[5:]))
+    names = n_rec * (name_bytes // max(n_reads, 1))
+    up = {"records": 128 * n_rec, "record_offsets": 32 * n_rec, "ops": 4 * ops, "md_and_blobs": md + host_blob, "names": names, "qualities": qual}
+    return {"records": n_rec, "up": up, "up_total": sum(up.values()), "down_text": len(text)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--lib", default=None, help="load this libbm2.so instead of the tree's")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--variants", default="off,on")
+    ap.add_argument("--pairs", type=int, default=500000)
+    ap.add_argument("--genome-mbp", type=int, default=int(os.environ.get("BM2_BENCH_GENOME_MBP", 3100)))
+    ap.add_argument("--workdir", default=os.environ.get("BM2_BENCH_WORKDIR", "/tmp/bm2_bench"))
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--once", action="store_true")
+    a = ap.parse_args()
+    res = {}
+    if a.parent_lib:                                             # the baseline first, in a process of its own
+        tmp = a.out + ".parent.json"
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--out", tmp, "--lib", a.parent_lib, "--variants", "off", "--pairs", str(a.pairs),
+                               "--genome-mbp", str(a.genome_mbp), "--workdir", a.workdir, "--calls", str(a.calls), "--threads", str(a.threads)])
+        res["parent"] = json.load(open(tmp))
+        os.remove(tmp)
+    import bench
+    import bm2
+    if a.lib:
+        bm2.LIB_PATH = a.lib
+    os.makedirs(a.workdir, exist_ok=True)
+    prefix, contigs = bench.prepare_genome(a.workdir, a.genome_mbp, bench.SEED)
+    fa, fb = os.path.join(a.workdir, "ab_1.fq"), os.path.join(a.workdir, "ab_2.fq")
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_chunk.py"), prefix + ".contigs.npz", "901", str(a.pairs), "150", fa, fb, "s_"])
+    t1, t2 = open(fa, "rb").read(), open(fb, "rb").read()
+    os.remove(fa); os.remove(fb)
+    ctx = bm2.Context(0, prefix)
+    opt = bm2.default_opt()
+    ch = bm2.FastqChunk(t1, t2, 16)
+    ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
+    aln, aln_off = ctx.batch_download_alnregs()
+    variants = a.variants.split(",")
+    flag = {"off": 0, "on": getattr(bm2, "SAM_F_DEVICE_TEXT", 0)}
+    bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
+    so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
+    if a.once:
+        txt = ctx.sam(ch, opt, so["on"], aln, aln_off, 0, True, out=bufs["on"].a)
+        print("[ab] one bit-on call: %d bytes, counters %s" % (len(txt), bm2.sam_text_stats()), file=sys.stderr)
+        return
+    wall = {v: [] for v in variants}
+    cpu = {v: [] for v in variants}
+    ph = {v: [] for v in variants}
+    counters, first = None, None
+    os.environ["BM2_TAIL_PROF"] = "1"
+    for rep in range(2 + a.calls):
+        texts = {}
+        for v in variants:
+            c0 = cpu_s(); t0 = time.perf_counter()
+            with Stderr() as err:
+                txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, True, out=bufs[v].a)
+            dt, dc = time.perf_counter() - t0, cpu_s() - c0
+            texts[v] = txt
+            if v == "on":
+                counters = bm2.sam_text_stats()
+            if rep >= 2:
+                wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
+        if len(variants) == 2:
+            assert len(texts["off"]) == len(texts["on"]) and (texts["off"] == texts["on"]).all(), "call %d: the two texts differ" % rep
+        if first is None:
+            first = texts[variants[0]].tobytes()
+        print("[ab] call %d: %s" % (rep, {v: "%.1f ms" % (wall[v][-1] if wall[v] else 0.0) for v in variants}), file=sys.stderr, flush=True)
+    mine = {"reads": ch.n_reads, "text_bytes": len(first), "threads": a.threads, "lib": a.lib or "tree", "variants": {}}
+    for v in variants:
+        keys = sorted(set(k for p in ph[v] for k in p))
+        mine["variants"][v] = {"wall_ms": spread(wall[v]), "cpu_s": spread(cpu[v]),
+                               "phases_ms_median": {k: float(np.median([p.get(k, 0.0) for p in ph[v]])) for k in keys}}
+    if counters is not None:
+        mine["text_stats"] = dict(zip(("records", "device_bytes", "host_bytes"), counters))
+        name_bytes = sum(len(n) for n in ch.names())
+        mine["pcie"] = pcie_ledger(first, ch.n_reads, name_bytes, counters[2])
+    res.update(mine) if not a.parent_lib else res.update({"new": mine})
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)
+    print(json.dumps(res if not a.parent_lib else {"parent": {k: res["parent"]["variants"]["off"][k] for k in ("wall_ms", "cpu_s")},
+                                                   "new": {v: {k: mine["variants"][v][k] for k in ("wall_ms", "cpu_s")} for v in variants}}))
+
+
+if __name__ == "__main__":
+    main()

@@ -61,6 +61,17 @@ class SamOpt(C.Structure):
 SAM_F_DEVICE_TEXT = 0x01000000      # BM2_SAM_F_DEVICE_TEXT: sam_*_dev make records and the device formats the text (off by default)
 
 
+SAM_F_DEVICE_DECIDE = 0x02000000    # BM2_SAM_F_DEVICE_DECIDE: sam_pe with a context takes the pairs' decisions from bm2_pe_decide_dev (off by default)
+
+
+class PairPlan(C.Structure):        # bm2_pairplan_t (include/bm2.h), 32 bytes
+    _fields_ = [("z", C.c_int32 * 2), ("n_pri", C.c_int32 * 2), ("q_se", C.c_int32 * 2), ("extra_flag", C.c_int32), ("paired", C.c_int32)]
+
+
+assert C.sizeof(PairPlan) == 32
+PAIRPLAN_DT = np.dtype([("z", "<i4", (2,)), ("n_pri", "<i4", (2,)), ("q_se", "<i4", (2,)), ("extra_flag", "<i4"), ("paired", "<i4")])
+
+
 class SamRec(C.Structure):          # bm2_samrec_t (include/bm2.h), 128 bytes
     _fields_ = [("read", C.c_int32), ("flag", C.c_int32), ("rid", C.c_int32), ("mapq", C.c_int32), ("pos", C.c_int64),
                 ("mrid", C.c_int32), ("rnext_eq", C.c_int32), ("mpos", C.c_int64), ("tlen", C.c_int64),
@@ -108,7 +119,7 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_last_error", "bm2_device_count", "bm2_set_stream_priority", "bm2_host_cpus", "bm2_host_alloc", "bm2_host_free", "bm2_bsw", "bm2_bsw_upload", "bm2_bsw_run", "bm2_bsw_download", "bm2_smem", "bm2_sal", "bm2_seed_chain_extend",
            "bm2_batch_upload", "bm2_batch_run", "bm2_batch_stats", "bm2_batch_download", "bm2_batch_kernel_ms", "bm2_batch_parts",
            "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats",
-           "bm2_sam_format_dev", "bm2_sam_text_stats"]
+           "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats"]
 
 _lib = None
 
@@ -476,6 +487,10 @@ class Context:
             _chk(rc, "bm2_sam_pe_dev" if paired else "bm2_sam_se_dev")
             return buf[:need.value]                              # a uint8 view of the buffer the library wrote into (no copy); bytes(x) / x.tobytes() for text
 
+    def pe_decide(self, opt, sam_opt, hits, hit_off, pes, first_pair=0):
+        """bm2_pe_decide_dev: see pe_decide()."""
+        return pe_decide(None, opt, sam_opt, hits, hit_off, pes, first_pair, ctx=self)
+
     def sam_format(self, so, enc, off, ln, names, recs, cigar=(), side=b"", quals=None, out=None):
         """bm2_sam_format_dev: decided records (a sequence of SamRec; offsets into `cigar` / `side`) -> their SAM lines, formatted on
         the device, as bytes.  out: the caller's uint8 buffer (default: the size is asked for first); when it is too small the Bm2Error
@@ -629,6 +644,37 @@ def sam_text_stats():
     L.bm2_sam_text_stats.restype = None
     L.bm2_sam_text_stats(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def sam_decide_stats():
+    """(pairs, hits, pairs_heavy) the decide kernels of the last call worked on (pe_decide with a context, or a tail with
+    SAM_F_DEVICE_DECIDE); heavy = the pairs that took the wavefront-per-pair form."""
+    v = [C.c_int64(0) for _ in range(3)]
+    L = lib()
+    L.bm2_sam_decide_stats.restype = None
+    L.bm2_sam_decide_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def pe_decide(index_prefix, opt, sam_opt, hits, hit_off, pes, first_pair=0, ctx=None):
+    """The decisions of mem_sam_pe for pairs whose hit lists are final (bm2_pe_decide; with ctx = a Context holding the index:
+    bm2_pe_decide_dev, the same on the device).  hits: ALNREG_DT, lists 2p and 2p + 1 of pair p delimited by hit_off (2 n_pairs + 1
+    entries); pes: 4 PeStat.  -> (the hits reordered and annotated, a PAIRPLAN_DT array); the caller's arrays are not touched."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    n_pairs = (len(hit_off) - 1) // 2
+    a = np.ascontiguousarray(hits, ALNREG_DT).copy()
+    plans = np.zeros(max(n_pairs, 1), PAIRPLAN_DT)
+    pq = (PeStat * 4)(*pes)
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    tail = (C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data), C.c_int64(first_pair), pq,
+            C.c_void_p(plans.ctypes.data))
+    if ctx is not None:
+        _chk(L.bm2_pe_decide_dev(C.c_void_p(ctx.h), *tail), "bm2_pe_decide_dev")
+    else:
+        with _DescOf(index_prefix) as d:
+            _chk(L.bm2_pe_decide(C.byref(d), *tail), "bm2_pe_decide")
+    return a, plans[:n_pairs]
 
 
 def sam_rescue_stats():

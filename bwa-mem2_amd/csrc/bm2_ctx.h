@@ -38,6 +38,8 @@ struct bm2_ctx {
     void *d_ann_names = nullptr, *d_ann_name_off = nullptr;
     // workspaces of bm2_sam_format_dev: inputs (records, ops, side bytes, packed names / qualities), sizes and offsets, the text
     DevBuf b_txt_in, b_txt_pos, b_txt_out, b_txt_enc, b_txt_scan;
+    // workspaces of bm2_pe_decide_dev (decide.hip): packed hits + offsets + tables, results, binning + the heavy pairs' lists, two scans
+    DevBuf b_dc_in, b_dc_out, b_dc_work, b_dc_scan, b_dc_scan2;
     void *txt_pin = nullptr; size_t txt_pin_cap = 0;              // page-locked staging of the packed names / qualities
     // the host array whose copy b_ref holds since the CIGAR batch of the SAM tail call in progress (NULL: none); the text of the same call reads it there
     const void *tail_enc = nullptr; size_t tail_enc_bytes = 0;
@@ -59,7 +61,7 @@ struct bm2_ctx {
     // Which side streams share a HARDWARE QUEUE (two launches on one queue run one after the other, whatever their streams): measured when the streams
     // are made (bm2_side_streams: a spinning one-lane kernel on every stream at once, the ones whose intervals do not overlap sit on one queue).
     // side_group[i] = the queue class of side stream i, group_rep[g] = the first stream of class g; n_side_groups = 0: not known (every stream its own).
-    int side_group[12] = {}, group_rep[12] = {}, n_side_groups = 0;
+    int side_group[13] = {}, group_rep[13] = {}, n_side_groups = 0;      // (13: the probe classifies the main stream with the twelve)
     // what the extension stage of the last batch saw (page-locked; written by an asynchronous copy at the end of the stage): per phase the
     // seeds of every LDS class and the reads left pending.  The next batch sizes its launches and picks its number of lazy rounds with it.
 #define BM2_EXT_PHASES 8

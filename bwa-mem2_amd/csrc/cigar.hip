@@ -107,9 +107,9 @@ static __device__ __forceinline__ void cg_nm_md(const uint32_t *cg, int ncg, QF 
                 const int nk = len - i0 < 8 ? len - i0 : 8;
                 uint32_t tw = RF8(y + i0, nk);
 #pragma nounroll
-                for (int k = 0; k < nk; ++k, tw >>= 4) {
+                for (int j = 0; j < nk; ++j, tw >>= 4) {
                     const int rb_ = (int)(tw & 15u);
-                    if (Q(x + i0 + k) != rb_) { nmd = put_dec(md, nmd, u); md[nmd++] = int2base[rb_]; ++n_mm; u = 0; }
+                    if (Q(x + i0 + j) != rb_) { nmd = put_dec(md, nmd, u); md[nmd++] = int2base[rb_]; ++n_mm; u = 0; }
                     else ++u;
                 }
             }

@@ -46,6 +46,24 @@ struct bm2h_text_scope {
     bm2h_text_scope(bm2_ctx *const *ctx, int n);
     ~bm2h_text_scope();
 };
+// The pairing decisions of one chunk (bm2_pe_decide_dev's arguments after the context).  Set through bm2h_decide_hook for the calling
+// thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_DECIDE, the CIGAR session of bm2h_sam_pe applies the rescue results on the
+// host threads, gathers every pair's lists into one array, calls the hook once and puts the lists back.  0 = success.
+typedef int (*bm2h_decide_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
+                                    const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
+int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off);       // non-negative, non-decreasing, every list below 2^30 hits
+struct bm2h_decide_hook {
+    bm2h_decide_hook(bm2h_decide_batch_fn fn, void *user);
+    ~bm2h_decide_hook();
+};
+// The device's hook (decide.hip; user = bm2h_text_ctxs: the pairs are cut into contiguous parts, one context and host thread per part)
+// and the scope the _dev entry points of the paired tail open around their bm2h_sam_pe call.
+int bm2h_dev_decide_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
+                          const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
+struct bm2h_decide_scope {
+    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_decide_hook hook;
+    bm2h_decide_scope(bm2_ctx *const *ctx, int n);
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -354,6 +354,8 @@ thread_local RecSink *t_rec = nullptr;                          // set while a t
 thread_local int t_rec_base = 0, t_rec_read = 0;                                // first read of the pair / the read whose lines are being made (the callers of aln2sam say)
 thread_local bm2h_text_batch_fn t_text_fn = nullptr;            // the calling thread's hook (bm2h_text_hook)
 thread_local void *t_text_user = nullptr;
+thread_local bm2h_decide_batch_fn t_decide_fn = nullptr;        // the calling thread's hook (bm2h_decide_hook)
+thread_local void *t_decide_user = nullptr;
 
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
 int reg2aln_band(const bm2_opt *opt, int qb, int qe, int64_t rb, int64_t re, int truesc, int w_hit) {
@@ -1301,11 +1303,9 @@ struct ReadIO { const char *name, *comment, *qual; int l_seq; const uint8_t *seq
 // and only reads the lists, so a CIGAR session can run it twice (once to note the hits it asks for, once to print) on the same state.
 struct PairPlan { int z[2] = { 0, 0 }, n_pri[2] = { 0, 0 }, q_se[2] = { 0, 0 }, extra_flag = 1; bool paired = false; };
 
-void pe_decide(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const int32_t *ann_len, const PeStat pes[4], uint64_t id,
-               const ReadIO s[2], HitList a[2], const RescueTask *pre, int n_pre, RescueStats *st, PairPlan &P) {
-    int o, subo, n_sub;
-    P = PairPlan();
-    int *z = P.z, *n_pri = P.n_pri, *q_se = P.q_se;
+// (in two steps, so that the second can run elsewhere: BM2_SAM_F_DEVICE_DECIDE, decide.hip)
+void pe_rescue(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const int32_t *ann_len, const PeStat pes[4],
+               const ReadIO s[2], HitList a[2], const RescueTask *pre, int n_pre, RescueStats *st) {
     if (!(so->flag & F_NO_RESCUE)) {
         static thread_local std::vector<bm2_alnreg_t> b[2];
         for (int i = 0; i < 2; ++i) rescue_anchors(so, a[i], b[i]);
@@ -1318,6 +1318,11 @@ void pe_decide(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const in
                 matesw(opt, so, R, ann_len, pes, &b[i][j], s[!i].l_seq, s[!i].seq, a[!i], pre ? pre + t : nullptr, t1 - t, st);
             }
     }
+}
+void pe_decide_marked(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const PeStat pes[4], uint64_t id, HitList a[2], PairPlan &P) {
+    int o, subo, n_sub;
+    P = PairPlan();
+    int *z = P.z, *n_pri = P.n_pri, *q_se = P.q_se;
     n_pri[0] = mark_primary_se(opt, (int)a[0].size(), a[0].data(), (int64_t)(id << 1 | 0));
     n_pri[1] = mark_primary_se(opt, (int)a[1].size(), a[1].data(), (int64_t)(id << 1 | 1));
     if (so->flag & F_PRIMARY5) { reorder_primary5(so->T, (int)a[0].size(), a[0].data()); reorder_primary5(so->T, (int)a[1].size(), a[1].data()); }
@@ -1356,6 +1361,11 @@ void pe_decide(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const in
             a[i][z[i]].secondary_all = -1;
         }
     }
+}
+void pe_decide(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const int32_t *ann_len, const PeStat pes[4], uint64_t id,
+               const ReadIO s[2], HitList a[2], const RescueTask *pre, int n_pre, RescueStats *st, PairPlan &P) {
+    pe_rescue(opt, so, R, ann_len, pes, s, a, pre, n_pre, st);
+    pe_decide_marked(opt, so, R, pes, id, a, P);
 }
 
 bool pe_emit(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const PeStat pes[4], const ReadIO s[2],
@@ -1608,6 +1618,47 @@ template <class F> int run_blocks_records(int n, int n_threads, const bm2_sam_op
 
 bm2h_text_hook::bm2h_text_hook(bm2h_text_batch_fn fn, void *user) { t_text_fn = fn; t_text_user = user; }
 bm2h_text_hook::~bm2h_text_hook() { t_text_fn = nullptr; t_text_user = nullptr; }
+bm2h_decide_hook::bm2h_decide_hook(bm2h_decide_batch_fn fn, void *user) { t_decide_fn = fn; t_decide_user = user; }
+bm2h_decide_hook::~bm2h_decide_hook() { t_decide_fn = nullptr; t_decide_user = nullptr; }
+
+int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) {
+    if (hit_off[0] < 0) { bm2_set_error("%s: hit_off[0] is negative", who); return BM2_EINVAL; }
+    for (int64_t i = 0; i < 2 * (int64_t)n_pairs; ++i) {
+        if (hit_off[i + 1] < hit_off[i]) { bm2_set_error("%s: hit_off decreases at list %lld", who, (long long)i); return BM2_EINVAL; }
+        if (hit_off[i + 1] - hit_off[i] > 0x3fffffff) { bm2_set_error("%s: list %lld is too long", who, (long long)i); return BM2_EINVAL; }
+    }
+    return BM2_OK;
+}
+
+// The decisions of mem_sam_pe for a batch of pairs whose lists are final (after mate rescue): the host form, and the oracle of decide.hip.
+extern "C" int bm2_pe_decide(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
+                             const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes_in[4], bm2_pairplan_t *plans) {
+    if (!idx || !opt || !so || n_pairs < 0 || !hit_off || !pes_in || (n_pairs > 0 && !plans) || !idx->ann_offset) { bm2_set_error("bm2_pe_decide: bad argument"); return BM2_EINVAL; }
+    int rc = bm2h_check_hit_off("bm2_pe_decide", n_pairs, hit_off);
+    if (rc) return rc;
+    if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("bm2_pe_decide: bad argument"); return BM2_EINVAL; }
+    Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
+    PeStat pes[4];
+    for (int d = 0; d < 4; ++d) { pes[d].low = pes_in[d].low; pes[d].high = pes_in[d].high; pes[d].failed = pes_in[d].failed; pes[d].avg = pes_in[d].avg; pes[d].std = pes_in[d].std; }
+    int nt = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
+    const int blk = 256, n_blk = (n_pairs + blk - 1) / blk;
+    if (nt > n_blk) nt = n_blk;
+    if (nt < 1) nt = 1;
+    std::atomic<int> next(0);
+    run_threads(nt, [&]() {
+        for (int b; (b = next.fetch_add(1)) < n_blk;)
+            for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+                HitList a[2] = { view_of(hits, hit_off, 2 * pi), view_of(hits, hit_off, 2 * pi + 1) };
+                PairPlan P;
+                t_scratch.reset();
+                pe_decide_marked(opt, so, R, pes, (uint64_t)(first_pair + pi), a, P);
+                bm2_pairplan_t &o = plans[pi];
+                for (int k = 0; k < 2; ++k) { o.z[k] = P.z[k]; o.n_pri[k] = P.n_pri[k]; o.q_se[k] = P.q_se[k]; }
+                o.extra_flag = P.extra_flag; o.paired = P.paired ? 1 : 0;
+            }
+    });
+    return BM2_OK;
+}
 
 extern "C" void bm2_sam_opt_init(bm2_sam_opt *o) {
     if (!o) return;
@@ -1743,6 +1794,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         bm2_set_error("bm2_sam_pe: bad argument (reads must be interleaved pairs)"); return BM2_EINVAL;
     }
     if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_DECIDE) && (!t_decide_fn || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_DECIDE needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
     if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_sam_pe: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
@@ -1920,6 +1972,13 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         t_scratch.reset(); spill_sync(epoch);
         pe_decide(opt, so, R, idx->ann_len, pes, (uint64_t)((n_processed >> 1) + pi), io, lists + 2 * pi, pre, n_pre, batch ? &g_rescue : nullptr, P);
     };
+    auto rescue_only = [&](int pi) {                              // the first half of `decide` (BM2_SAM_F_DEVICE_DECIDE: the second runs as a batch)
+        ReadIO io[2]; io_of(pi, io);
+        const RescueTask *pre = batch ? tasks.data() + task_off[(size_t)pi] : nullptr;
+        const int n_pre = batch ? (int)(task_off[(size_t)pi + 1] - task_off[(size_t)pi]) : 0;
+        t_scratch.reset(); spill_sync(epoch);
+        pe_rescue(opt, so, R, idx->ann_len, pes, io, lists + 2 * pi, pre, n_pre, batch ? &g_rescue : nullptr);
+    };
     auto emit = [&](int pi, const PairPlan &P, Text &part) {
         ReadIO io[2]; io_of(pi, io);
         t_scratch.reset();                                       // (the pair's CIGARs, XA strings and record lists: gone with the next pair)
@@ -1939,12 +1998,58 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         const int blk = 256, n_blk = (n_pairs + blk - 1) / blk;
         std::vector<std::vector<int32_t>> recs((size_t)n_blk);
         std::atomic<int> next(0), failed(-1);
+        const bool dev_decide = (so->flag & BM2_SAM_F_DEVICE_DECIDE) != 0;
+        if (dev_decide) {                                        // rescue on the host threads, then every pair's decisions in one call of the hook
+            run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                for (int b; (b = next.fetch_add(1)) < n_blk;)
+                    for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) rescue_only(pi);
+                flush_tallies();
+            });
+            next = 0;
+            prof.mark("rescue apply");
+            static thread_local std::vector<bm2_alnreg_t> flat_of_this_thread;
+            static thread_local std::vector<int64_t> flat_off_of_this_thread;
+            static thread_local std::vector<bm2_pairplan_t> dplans_of_this_thread;
+            std::vector<bm2_alnreg_t> &flat = flat_of_this_thread;
+            std::vector<int64_t> &flat_off = flat_off_of_this_thread;
+            std::vector<bm2_pairplan_t> &dplans = dplans_of_this_thread;
+            if (flat_off.size() < (size_t)n + 1) flat_off.resize((size_t)n + 1);
+            if (dplans.size() < (size_t)n_pairs) dplans.resize((size_t)n_pairs);
+            flat_off[0] = 0;
+            for (int i = 0; i < n; ++i) flat_off[(size_t)i + 1] = flat_off[(size_t)i] + lists[i].n;
+            if (flat.size() < (size_t)flat_off[(size_t)n] + 1) flat.resize((size_t)flat_off[(size_t)n] + 1);
+            auto copy_lists = [&](bool back) {
+                std::atomic<int> nx(0);
+                run_threads(n_threads < n / 8192 + 1 ? n_threads : n / 8192 + 1, [&]() {
+                    for (int lo; (lo = nx.fetch_add(8192)) < n;)
+                        for (int i = lo; i < n && i < lo + 8192; ++i) {
+                            if (!lists[i].n) continue;
+                            if (back) memcpy(lists[i].p, flat.data() + flat_off[(size_t)i], sizeof(bm2_alnreg_t) * (size_t)lists[i].n);
+                            else memcpy(flat.data() + flat_off[(size_t)i], lists[i].p, sizeof(bm2_alnreg_t) * (size_t)lists[i].n);
+                        }
+                });
+            };
+            copy_lists(false);
+            prof.mark("decide gather");
+            bm2_pestat pq[4];
+            for (int d = 0; d < 4; ++d) { pq[d].low = pes[d].low; pq[d].high = pes[d].high; pq[d].failed = pes[d].failed; pq[d].pad = 0; pq[d].avg = pes[d].avg; pq[d].std = pes[d].std; }
+            const int rc = t_decide_fn(t_decide_user, opt, so, n_pairs, flat.data(), flat_off.data(), n_processed >> 1, pq, dplans.data());
+            if (rc) return rc;
+            prof.mark("decide batch");
+            copy_lists(true);
+            for (int pi = 0; pi < n_pairs; ++pi) {
+                PairPlan &P = plans[(size_t)pi]; const bm2_pairplan_t &o = dplans[(size_t)pi];
+                for (int k = 0; k < 2; ++k) { P.z[k] = o.z[k]; P.n_pri[k] = o.n_pri[k]; P.q_se[k] = o.q_se[k]; }
+                P.extra_flag = o.extra_flag; P.paired = o.paired != 0;
+            }
+            prof.mark("decide scatter");
+        }
         run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
             Text sink;
             for (int b; (b = next.fetch_add(1)) < n_blk;) {
                 t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
                 for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
-                    decide(pi, plans[(size_t)pi]);
+                    if (!dev_decide) decide(pi, plans[(size_t)pi]);
                     if (!emit(pi, plans[(size_t)pi], sink)) { int e = -1; failed.compare_exchange_strong(e, pi); }
                     sink.clear();
                 }
@@ -1987,6 +2092,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         bm2_set_error("bm2_sam_se: bad argument"); return BM2_EINVAL;
     }
     if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_DECIDE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_DECIDE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);

@@ -364,6 +364,31 @@ int bm2_sam_format_dev(bm2_ctx *c, const bm2_sam_opt *so, const bm2_reads *reads
  * arrived pre-formatted (the blobs). */
 void bm2_sam_text_stats(int64_t *records, int64_t *device_bytes, int64_t *host_bytes);
 
+/* ---- pairing decisions on the device (decide.hip): what mem_sam_pe (bwamem_pair.cpp:353-551) does to a pair's two hit lists AFTER
+ * mate rescue and before any text: mem_mark_primary_se on both lists (ids (first_pair + p) << 1 | end), mem_reorder_primary5 under
+ * MEM_F_PRIMARY5, mem_pair, q_pe, the two q_se of mem_approx_mapq_se, the sub / secondary = -2 rewrite of the chosen hits and the
+ * primary / secondary switch of secondary_all.  Lists 2p and 2p + 1 of pair p are hits[hit_off[2p] .. hit_off[2p + 1]) and
+ * hits[hit_off[2p + 1] .. hit_off[2p + 2]); hit_off (2 n_pairs + 1 entries) must be non-negative and non-decreasing, and
+ * hit_off[2 n_pairs] is the length of hits (checked before anything follows an offset).  The hits are reordered and annotated IN
+ * PLACE, every field travelling with its hit (pad and hash included), as bm2_sam_se documents for its alnregs; plans[p] is the
+ * pair's outcome.  bm2_pe_decide is the host code of bm2_sam_pe behind a C name and the oracle of bm2_pe_decide_dev, which takes
+ * l_pac and the contig offsets from its context (BM2_EINVAL for a context created without an index) and decides EVERY pair on the
+ * device, whatever its list lengths.  No transcendental function runs there: the host tabulates the insert-size term of mem_pair
+ * per live orientation over [low, high] with its own libm, per call; the four spans together may not exceed 2^22 entries, nor may a
+ * hit's span or seedcov (the arguments of log in mem_approx_mapq_se): BM2_EUNSUP otherwise (the host form has neither limit). */
+typedef struct { int32_t z[2], n_pri[2], q_se[2], extra_flag, paired; } bm2_pairplan_t;     /* 32 B */
+int bm2_pe_decide(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
+                  const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
+int bm2_pe_decide_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
+                      const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
+/* A library-private bit of bm2_sam_opt.flag, combinable with BM2_SAM_F_DEVICE_TEXT: bm2_sam_pe_dev and bm2_sam_pe_dev_multi apply the
+ * mate-rescue results on the host and then take every pair's decisions from bm2_pe_decide_dev on their context(s) in one batch.
+ * Same bytes.  Off by default.  bm2_sam_pe and the single-end entry points answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_DECIDE 0x02000000
+/* What the decide kernels of the last call on this process worked on: pairs, hits, and the pairs that took the wavefront-per-pair
+ * form (more than 16 hits in all). */
+void bm2_sam_decide_stats(int64_t *pairs, int64_t *hits, int64_t *pairs_heavy);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

@@ -6,6 +6,8 @@ spread of wall ms and of process CPU-s per call (resource.getrusage), the phases
 bm2_sam_text_stats and the bytes that cross PCIe each way, counted from the chunk.  --parent-lib: a second process of this tool loads
 that library (the parent commit's build) and times its bit-off path on the same chunk first: the baseline for "CPU-s per chunk".
     python tools/gpu/tail_text_ab.py --out profiles/sam_text_dev_ab.json [--parent-lib PATH] [--pairs 500000] [--genome-mbp 3100] [--calls 10]
+--bit text|decide|both: which opt-in bit the "on" variant sets (BM2_SAM_F_DEVICE_TEXT, BM2_SAM_F_DEVICE_DECIDE: the pairs' decisions from
+bm2_pe_decide_dev, or the two together); with decide the result also holds bm2_sam_decide_stats and the bytes the decisions move.
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -97,6 +99,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both"))
     a = ap.parse_args()
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
@@ -121,7 +124,8 @@ def main():
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
-    flag = {"off": 0, "on": getattr(bm2, "SAM_F_DEVICE_TEXT", 0)}
+    bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if a.bit in ("text", "both") else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if a.bit in ("decide", "both") else 0)
+    flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
     if a.once:
@@ -131,7 +135,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first = None, None
+    counters, first, decided = None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -141,8 +145,10 @@ def main():
                 txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, True, out=bufs[v].a)
             dt, dc = time.perf_counter() - t0, cpu_s() - c0
             texts[v] = txt
-            if v == "on":
+            if v == "on" and a.bit != "decide":
                 counters = bm2.sam_text_stats()
+            if v == "on" and a.bit != "text":
+                decided = bm2.sam_decide_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -150,7 +156,7 @@ def main():
         if first is None:
             first = texts[variants[0]].tobytes()
         print("[ab] call %d: %s" % (rep, {v: "%.1f ms" % (wall[v][-1] if wall[v] else 0.0) for v in variants}), file=sys.stderr, flush=True)
-    mine = {"reads": ch.n_reads, "text_bytes": len(first), "threads": a.threads, "lib": a.lib or "tree", "variants": {}}
+    mine = {"reads": ch.n_reads, "text_bytes": len(first), "threads": a.threads, "lib": a.lib or "tree", "bit": a.bit, "variants": {}}
     for v in variants:
         keys = sorted(set(k for p in ph[v] for k in p))
         mine["variants"][v] = {"wall_ms": spread(wall[v]), "cpu_s": spread(cpu[v]),
@@ -159,6 +165,11 @@ def main():
         mine["text_stats"] = dict(zip(("records", "device_bytes", "host_bytes"), counters))
         name_bytes = sum(len(n) for n in ch.names())
         mine["pcie"] = pcie_ledger(first, ch.n_reads, name_bytes, counters[2])
+    if decided is not None:                                      # (decide.hip: 56 B a hit and 8 B a list up, the tables aside; 32 B a hit and 32 B a pair down)
+        pairs, hits, heavy = decided
+        mine["decide_stats"] = {"pairs": pairs, "hits": hits, "pairs_heavy": heavy}
+        mine["decide_pcie"] = {"up": 56 * hits + 8 * (2 * pairs + 1), "down": 32 * hits + 32 * pairs,
+                               "up_per_pair": (56 * hits + 16 * pairs) / max(pairs, 1), "down_per_pair": (32 * hits + 32 * pairs) / max(pairs, 1)}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

@@ -64,6 +64,24 @@ SAM_F_DEVICE_TEXT = 0x01000000      # BM2_SAM_F_DEVICE_TEXT: sam_*_dev make reco
 SAM_F_DEVICE_DECIDE = 0x02000000    # BM2_SAM_F_DEVICE_DECIDE: sam_pe with a context takes the pairs' decisions from bm2_pe_decide_dev (off by default)
 
 
+SAM_F_DEVICE_RESCUE = 0x04000000    # BM2_SAM_F_DEVICE_RESCUE: sam_pe with a context applies the mate-rescue results on the device (off by default)
+
+
+class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
+    _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
+
+
+class RescueTask(C.Structure):      # bm2_rescue_task_t (include/bm2.h), 64 bytes
+    _fields_ = [("pair", C.c_int32), ("j", C.c_int32), ("end", C.c_int32), ("r", C.c_int32), ("rb", C.c_int64), ("re", C.c_int64),
+                ("res", KswResult), ("pad", C.c_int32)]
+
+
+assert C.sizeof(RescueTask) == 64
+RESCUE_TASK_DT = np.dtype([("pair", "<i4"), ("j", "<i4"), ("end", "<i4"), ("r", "<i4"), ("rb", "<i8"), ("re", "<i8"),
+                           ("res", "<i4", (7,)), ("pad", "<i4")])
+assert RESCUE_TASK_DT.itemsize == 64
+
+
 class PairPlan(C.Structure):        # bm2_pairplan_t (include/bm2.h), 32 bytes
     _fields_ = [("z", C.c_int32 * 2), ("n_pri", C.c_int32 * 2), ("q_se", C.c_int32 * 2), ("extra_flag", C.c_int32), ("paired", C.c_int32)]
 
@@ -119,7 +137,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_last_error", "bm2_device_count", "bm2_set_stream_priority", "bm2_host_cpus", "bm2_host_alloc", "bm2_host_free", "bm2_bsw", "bm2_bsw_upload", "bm2_bsw_run", "bm2_bsw_download", "bm2_smem", "bm2_sal", "bm2_seed_chain_extend",
            "bm2_batch_upload", "bm2_batch_run", "bm2_batch_stats", "bm2_batch_download", "bm2_batch_kernel_ms", "bm2_batch_parts",
            "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats",
-           "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats"]
+           "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats",
+           "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats"]
 
 _lib = None
 
@@ -461,8 +480,9 @@ class Context:
         _chk(L.bm2_batch_download_alnregs(self.h, out.ctypes.data, len(out), aln_off.ctypes.data, C.byref(n)), "bm2_batch_download_alnregs")
         return out[:n.value], aln_off
 
-    def sam(self, chunk, opt, so, alnregs, aln_off, n_processed=0, paired=True, out=None):
-        """SAM alignment lines of a chunk (bm2_sam_pe_dev / bm2_sam_se_dev: rescue and CIGAR alignments as device batches) -> uint8 array."""
+    def sam(self, chunk, opt, so, alnregs, aln_off, n_processed=0, paired=True, out=None, also=()):
+        """SAM alignment lines of a chunk (bm2_sam_pe_dev / bm2_sam_se_dev: rescue and CIGAR alignments as device batches) -> uint8 array.
+        also: further contexts holding the index (paired input: bm2_sam_pe_dev_multi over this context and those)."""
         L = lib()
         alnregs = np.ascontiguousarray(alnregs, ALNREG_DT)
         aln_off = np.ascontiguousarray(aln_off, np.int64)
@@ -472,7 +492,12 @@ class Context:
             cap = len(out)                                      # a caller's buffer, reused from chunk to chunk (no fresh pages to fault in)
         while True:
             buf = out if out is not None and len(out) == cap else np.empty(cap, np.uint8)
-            if paired:
+            if paired and also:
+                hs = (C.c_void_p * (1 + len(also)))(self.h, *[c.h for c in also])
+                rc = L.bm2_sam_pe_dev_multi(hs, C.c_int(1 + len(also)), C.byref(self._desc), C.byref(opt), C.byref(so), C.byref(chunk.reads), C.byref(chunk.text),
+                                            C.c_void_p(alnregs.ctypes.data), C.c_void_p(aln_off.ctypes.data), C.c_int64(n_processed), None, None,
+                                            C.c_void_p(buf.ctypes.data), C.c_int64(cap), C.byref(need))
+            elif paired:
                 rc = L.bm2_sam_pe_dev(C.c_void_p(self.h), C.byref(self._desc), C.byref(opt), C.byref(so), C.byref(chunk.reads), C.byref(chunk.text),
                                       C.c_void_p(alnregs.ctypes.data), C.c_void_p(aln_off.ctypes.data), C.c_int64(n_processed), None, None,
                                       C.c_void_p(buf.ctypes.data), C.c_int64(cap), C.byref(need))
@@ -486,6 +511,10 @@ class Context:
                 continue
             _chk(rc, "bm2_sam_pe_dev" if paired else "bm2_sam_se_dev")
             return buf[:need.value]                              # a uint8 view of the buffer the library wrote into (no copy); bytes(x) / x.tobytes() for text
+
+    def pe_rescue_apply(self, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off):
+        """bm2_pe_rescue_apply_dev: see pe_rescue_apply()."""
+        return pe_rescue_apply(None, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off, ctx=self)
 
     def pe_decide(self, opt, sam_opt, hits, hit_off, pes, first_pair=0):
         """bm2_pe_decide_dev: see pe_decide()."""
@@ -675,6 +704,71 @@ def pe_decide(index_prefix, opt, sam_opt, hits, hit_off, pes, first_pair=0, ctx=
         with _DescOf(index_prefix) as d:
             _chk(L.bm2_pe_decide(C.byref(d), *tail), "bm2_pe_decide")
     return a, plans[:n_pairs]
+
+
+def sam_rescue_apply_stats():
+    """(pairs, tasks, hits_added, pairs_redone) of the last rescue-apply call (pe_rescue_apply in either form, or a tail with
+    SAM_F_DEVICE_RESCUE)."""
+    v = [C.c_int64(0) for _ in range(4)]
+    L = lib()
+    L.bm2_sam_rescue_apply_stats.restype = None
+    L.bm2_sam_rescue_apply_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes):
+    """The mate-rescue alignments mem_sam_pe may ask for in a batch of pairs, judged on the lists as they stand (bm2_pe_rescue_plan,
+    host only) -> (a RESCUE_TASK_DT array in (pair, end, j, r) order with zeroed results, task_off[n_pairs + 1])."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    n_pairs = (len(hit_off) - 1) // 2
+    a = np.ascontiguousarray(hits, ALNREG_DT)
+    ln = np.ascontiguousarray(read_len, np.int32)
+    pq = (PeStat * 4)(*pes)
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    task_off = np.zeros(n_pairs + 1, np.int64)
+    need = C.c_int64(0)
+    cap = 0
+    with _DescOf(index_prefix) as d:
+        while True:
+            tasks = np.zeros(max(cap, 1), RESCUE_TASK_DT)
+            rc = L.bm2_pe_rescue_plan(C.byref(d), C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data),
+                                      C.c_void_p(ln.ctypes.data), pq, C.c_void_p(tasks.ctypes.data), C.c_int64(cap), C.c_void_p(task_off.ctypes.data), C.byref(need))
+            if rc == BM2_ECAP:
+                cap = need.value
+                continue
+            _chk(rc, "bm2_pe_rescue_plan")
+            return tasks[:need.value], task_off
+
+
+def pe_rescue_apply(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off, ctx=None):
+    """What mem_sam_pe's mate rescue does to the hit lists of a batch of pairs, given the planned tasks with their results
+    (bm2_pe_rescue_apply; with ctx = a Context holding the index: bm2_pe_rescue_apply_dev, the same on the device).
+    -> (the grown lists as one ALNREG_DT array, out_off[2 n_pairs + 1], redo[n_pairs]); redo = 1: the pair needs an alignment that was
+    not planned, its lists are returned as they came."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    task_off = np.ascontiguousarray(task_off, np.int64)
+    n_pairs = (len(hit_off) - 1) // 2
+    a = np.ascontiguousarray(hits, ALNREG_DT)
+    t = np.ascontiguousarray(tasks, RESCUE_TASK_DT)
+    ln = np.ascontiguousarray(read_len, np.int32)
+    pq = (PeStat * 4)(*pes)
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    cap = len(a) + len(t) + 1
+    out = np.zeros(cap, ALNREG_DT)
+    out_off = np.zeros(2 * n_pairs + 1, np.int64)
+    redo = np.zeros(max(n_pairs, 1), np.int32)
+    need = C.c_int64(0)
+    tail = (C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data), C.c_void_p(ln.ctypes.data), pq,
+            C.c_void_p(t.ctypes.data), C.c_void_p(task_off.ctypes.data), C.c_void_p(out.ctypes.data), C.c_int64(cap), C.c_void_p(out_off.ctypes.data),
+            C.c_void_p(redo.ctypes.data), C.byref(need))
+    if ctx is not None:
+        _chk(L.bm2_pe_rescue_apply_dev(C.c_void_p(ctx.h), *tail), "bm2_pe_rescue_apply_dev")
+    else:
+        with _DescOf(index_prefix) as d:
+            _chk(L.bm2_pe_rescue_apply(C.byref(d), *tail), "bm2_pe_rescue_apply")
+    return out[:need.value], out_off, redo[:n_pairs]
 
 
 def sam_rescue_stats():

@@ -39,8 +39,10 @@ struct bm2_ctx {
     // workspaces of bm2_sam_format_dev: inputs (records, ops, side bytes, packed names / qualities), sizes and offsets, the text
     DevBuf b_txt_in, b_txt_pos, b_txt_out, b_txt_enc, b_txt_scan;
     // workspaces of bm2_pe_decide_dev (decide.hip): packed hits + offsets + tables, results, binning + the heavy pairs' lists, two scans
-    DevBuf b_dc_in, b_dc_out, b_dc_work, b_dc_scan, b_dc_scan2;
-    void *txt_pin = nullptr; size_t txt_pin_cap = 0;              // page-locked staging of the packed names / qualities
+    DevBuf b_dc_in, b_dc_out, b_dc_work, b_dc_scan, b_dc_scan2, b_dc_pack, b_dc_final;      // (the last two: the resident form)
+    // workspaces of bm2_pe_rescue_apply_dev (rescue.hip): lists + tasks + offsets, the pairs' working slices, the grown lists, a scan
+    DevBuf b_rs_in, b_rs_work, b_rs_out, b_rs_scan;
+    void *txt_pin = nullptr; size_t txt_pin_cap = 0;             // page-locked staging of the packed names / qualities
     // the host array whose copy b_ref holds since the CIGAR batch of the SAM tail call in progress (NULL: none); the text of the same call reads it there
     const void *tail_enc = nullptr; size_t tail_enc_bytes = 0;
     // scratch for the S1/S2 entry points

@@ -432,6 +432,39 @@ __global__ __launch_bounds__(64) void k_decide_heavy(DcPrm P) {
     decide_pair<64>(G, P, p, A, B);
 }
 
+// ---- the resident form (BM2_SAM_F_DEVICE_RESCUE | BM2_SAM_F_DEVICE_DECIDE): the lists lie in HBM where rescue.hip's gather left them
+// k_decide_pack: what the host's pack loop does, a lane per hit; stat[0] = the largest argument log will see, stat[1] = 1 + a hit on no contig
+__global__ void k_decide_pack(const bm2_alnreg_t *__restrict__ H, int64_t n_hits, int n_seqs, DcIn *__restrict__ in, int *__restrict__ stat) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_hits) return;
+    const bm2_alnreg_t &h = H[i];
+    DcIn d;
+    d.rb = h.rb; d.re = h.re; d.qb = h.qb; d.qe = h.qe; d.rid = h.rid; d.score = h.score; d.csub = h.csub; d.sub_n = h.sub_n;
+    d.seedcov = h.seedcov; d.is_alt = h.is_alt; d.frac_rep = h.frac_rep; d.pad = 0;
+    in[i] = d;
+    const int64_t sr = h.re - h.rb;
+    int64_t top = h.qe - h.qb > sr ? h.qe - h.qb : (int64_t)(int)sr;
+    if (h.seedcov > top) top = h.seedcov;
+    if (top > DC_TAB_MAX) top = DC_TAB_MAX + 1;
+    if (top > 0) atomicMax(stat, (int)top);
+    if (h.rid < 0 || h.rid >= n_seqs) atomicMax(stat + 1, (int)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
+}
+// k_decide_permute: what the host's apply loop does, a 16-lane row per list: every list in the decided order, the six rewritten fields from
+// the kernels, everything else with its hit.  stat[2] = 1 + a pair whose permutation is broken.
+__global__ __launch_bounds__(256) void k_decide_permute(const bm2_alnreg_t *__restrict__ H, const DcOut *__restrict__ out, const int64_t *__restrict__ hit_off,
+                                                        int64_t n_lists, bm2_alnreg_t *__restrict__ fin, int *__restrict__ stat) {
+    const int64_t li = (int64_t)blockIdx.x * (256 / 16) + (threadIdx.x >> 4);
+    if (li >= n_lists) return;
+    const int64_t b0 = hit_off[li], k = hit_off[li + 1] - b0;
+    for (int64_t i = threadIdx.x & 15; i < k; i += 16) {
+        const DcOut r = out[b0 + i];
+        if (r.orig < 0 || r.orig >= k) { atomicMax(stat + 2, (int)((li >> 1) + 1)); continue; }
+        bm2_alnreg_t h = H[b0 + r.orig];
+        h.hash = r.hash; h.sub = r.sub; h.alt_sc = r.alt_sc; h.sub_n = r.sub_n; h.secondary = r.secondary; h.secondary_all = r.secondary_all;
+        fin[b0 + i] = h;
+    }
+}
+
 namespace {
 std::atomic<long long> g_dc_pairs{0}, g_dc_hits{0}, g_dc_heavy{0};
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -448,8 +481,10 @@ void step_thresholds(std::vector<int64_t> &thr) {
     }
 }
 
+// d_hits / d_off = NULL: the lists come from and go back to `hits` (host).  Otherwise the resident form: d_hits[hit_off[0] ..] and d_off (the
+// offsets from 0, as hit_off minus hit_off[0]) lie in HBM already, hit_off is their host copy, and the decided lists are written to `hits`.
 int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits, const int64_t *hit_off,
-               int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans) {
+               int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans, const bm2_alnreg_t *d_hits = nullptr, const int64_t *d_off = nullptr) {
     if (n_pairs == 0) return BM2_OK;
     int rc = bm2_check(hipSetDevice(c->device), "hipSetDevice");
     if (rc) return rc;
@@ -475,7 +510,21 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     if (out.size() < (size_t)n_hits + 1) out.resize((size_t)n_hits + 1);
     std::atomic<int64_t> log_top(0), bad_rid(-1);
     const int n_seqs = c->ix.n_seqs;
-    bm2_parallel_ranges(n_hits, 32768, nt, [&](int64_t lo, int64_t hi) {
+    int *d_stat = nullptr;
+    if (d_hits) {                                                // pack on the device; two numbers come back
+        if ((rc = bm2_reserve(c->b_dc_pack, up256((size_t)n_hits * sizeof(DcIn)) + 512))) return rc;
+        d_stat = (int *)((char *)c->b_dc_pack.p + up256((size_t)n_hits * sizeof(DcIn)));
+        if ((rc = bm2_check(hipMemsetAsync(d_stat, 0, 16, c->stream), "memset decide stat"))) return rc;
+        if (n_hits) {
+            hipLaunchKernelGGL(k_decide_pack, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, c->stream, d_hits, n_hits, n_seqs, (DcIn *)c->b_dc_pack.p, d_stat);
+            if ((rc = bm2_check(hipGetLastError(), "k_decide_pack launch"))) return rc;
+        }
+        int st[4] = { 0, 0, 0, 0 };
+        if ((rc = bm2_check(hipMemcpyAsync(st, d_stat, 16, hipMemcpyDeviceToHost, c->stream), "D2H decide stat"))) return rc;
+        if ((rc = bm2_check(hipStreamSynchronize(c->stream), "k_decide_pack"))) return rc;
+        log_top = st[0];
+        if (st[1]) { bm2_set_error("%s: hit %d lies on no contig of the context's index", who, st[1] - 1); return BM2_EINVAL; }
+    } else bm2_parallel_ranges(n_hits, 32768, nt, [&](int64_t lo, int64_t hi) {
         int64_t top = 0;
         for (int64_t i = lo; i < hi; ++i) {
             const bm2_alnreg_t &h = H[i];
@@ -490,7 +539,7 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
         int64_t seen = log_top.load();
         while (top > seen && !log_top.compare_exchange_weak(seen, top)) {}
     });
-    if (bad_rid.load() >= 0) { bm2_set_error("%s: hit %lld lies on no contig of the context's index (rid %d)", who, (long long)bad_rid.load(), H[bad_rid.load()].rid); return BM2_EINVAL; }
+    if (!d_hits && bad_rid.load() >= 0) { bm2_set_error("%s: hit %lld lies on no contig of the context's index (rid %d)", who, (long long)bad_rid.load(), H[bad_rid.load()].rid); return BM2_EINVAL; }
     if (log_top.load() > DC_TAB_MAX) { bm2_set_error("%s: a hit spans %lld bases (or has that seed coverage); above 2^22 the device form has no table of log", who, (long long)log_top.load()); return BM2_EUNSUP; }
     prof.mark("pack");
     // tables (the host's libm): the insert-size term of a pairing, log, the steps of 4.343 log(n + 1)
@@ -523,7 +572,7 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     for (int v = 0; v <= log_n; ++v) tab[(size_t)span + (size_t)v] = log((double)v);
     prof.mark("tables");
     // device buffers
-    const size_t in_b = up256((size_t)n_hits * sizeof(DcIn)), off_b = up256((size_t)(n_lists + 1) * 8), tab_b = up256(((size_t)span + (size_t)log_n + 1) * 8),
+    const size_t in_b = d_hits ? 0 : up256((size_t)n_hits * sizeof(DcIn)), off_b = up256((size_t)(n_lists + 1) * 8), tab_b = up256(((size_t)span + (size_t)log_n + 1) * 8),
                  thr_b = up256(thr.size() * 8);
     const size_t out_b = up256((size_t)n_hits * sizeof(DcOut)), plan_b = up256((size_t)n_pairs * sizeof(bm2_pairplan_t));
     const size_t flag_b = up256((size_t)n_pairs * 4), at_b = up256((size_t)(n_pairs + 1) * 8), list_b = up256((size_t)(n_heavy + 1) * 4),
@@ -532,7 +581,7 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     if ((rc = bm2_reserve(c->b_dc_out, out_b + plan_b + 256))) return rc;
     if ((rc = bm2_reserve(c->b_dc_work, 2 * flag_b + 2 * at_b + list_b + work_b + 256))) return rc;
     char *d = (char *)c->b_dc_in.p;
-    P.in = (const DcIn *)d; P.hit_off = (const int64_t *)(d + in_b); P.ptab = (const double *)(d + in_b + off_b); P.logtab = P.ptab + span;
+    P.in = d_hits ? (const DcIn *)c->b_dc_pack.p : (const DcIn *)d; P.hit_off = d_off ? d_off : (const int64_t *)(d + in_b); P.ptab = (const double *)(d + in_b + off_b); P.logtab = P.ptab + span;
     P.step_thr = (const int64_t *)(d + in_b + off_b + tab_b);
     P.out = (DcOut *)c->b_dc_out.p; P.plans = (bm2_pairplan_t *)((char *)c->b_dc_out.p + out_b);
     char *w = (char *)c->b_dc_work.p;
@@ -545,8 +594,8 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     P.a = opt->a; P.b = opt->b; P.o_del = opt->o_del; P.e_del = opt->e_del; P.o_ins = opt->o_ins; P.e_ins = opt->e_ins; P.min_seed_len = opt->min_seed_len;
     P.mask_level = opt->mask_level; P.coef_len = so->mapQ_coef_len; P.T = so->T; P.flag = so->flag; P.pen_unpaired = so->pen_unpaired; P.coef_fac = so->mapQ_coef_fac;
     P.log_n = log_n; P.n_step = (int32_t)thr.size();
-    if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.in, in.data(), (size_t)n_hits * sizeof(DcIn)))) return rc;
-    if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, off.data(), (size_t)(n_lists + 1) * 8))) return rc;
+    if (!d_hits && n_hits && (rc = bm2_copy_h2d(c, (void *)P.in, in.data(), (size_t)n_hits * sizeof(DcIn)))) return rc;
+    if (!d_off && (rc = bm2_copy_h2d(c, (void *)P.hit_off, off.data(), (size_t)(n_lists + 1) * 8))) return rc;
     if ((rc = bm2_copy_h2d(c, (void *)P.ptab, tab.data(), ((size_t)span + (size_t)log_n + 1) * 8))) return rc;
     if ((rc = bm2_copy_h2d(c, (void *)P.step_thr, thr.data(), thr.size() * 8))) return rc;
     prof.mark("H2D");
@@ -569,6 +618,22 @@ int decide_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     if ((rc = bm2_check(hipStreamSynchronize(c->stream), "k_decide"))) return rc;
     prof.mark("kernels");
     if (heavy_seen != n_heavy) { bm2_set_error("%s: the device binned %lld heavy pairs, the host counted %lld", who, (long long)heavy_seen, (long long)n_heavy); return BM2_ENODEV; }
+    if (d_hits) {                                                // the permutation on the device, the decided lists down once
+        if ((rc = bm2_reserve(c->b_dc_final, up256((size_t)n_hits * sizeof(bm2_alnreg_t)) + 256))) return rc;
+        hipLaunchKernelGGL(k_decide_permute, dim3((unsigned)((n_lists + 15) / 16)), dim3(256), 0, c->stream, d_hits, (const DcOut *)P.out, P.hit_off, n_lists,
+                           (bm2_alnreg_t *)c->b_dc_final.p, d_stat);
+        if ((rc = bm2_check(hipGetLastError(), "k_decide_permute launch"))) return rc;
+        int st[4] = { 0, 0, 0, 0 };
+        if ((rc = bm2_check(hipMemcpyAsync(st, d_stat, 16, hipMemcpyDeviceToHost, c->stream), "D2H decide stat"))) return rc;
+        if ((rc = bm2_check(hipStreamSynchronize(c->stream), "k_decide_permute"))) return rc;
+        prof.mark("permute");
+        if (st[2]) { bm2_set_error("%s: pair %d came back with a broken permutation", who, st[2] - 1); return BM2_ENODEV; }
+        if (n_hits && (rc = bm2_copy_d2h(c, H, c->b_dc_final.p, (size_t)n_hits * sizeof(bm2_alnreg_t)))) return rc;
+        if ((rc = bm2_copy_d2h(c, plans, P.plans, (size_t)n_pairs * sizeof(bm2_pairplan_t)))) return rc;
+        prof.mark("D2H");
+        g_dc_pairs += n_pairs; g_dc_hits += (long long)n_hits; g_dc_heavy += (long long)n_heavy;
+        return BM2_OK;
+    }
     if (n_hits && (rc = bm2_copy_d2h(c, out.data(), P.out, (size_t)n_hits * sizeof(DcOut)))) return rc;
     if ((rc = bm2_copy_d2h(c, plans, P.plans, (size_t)n_pairs * sizeof(bm2_pairplan_t)))) return rc;
     prof.mark("D2H");
@@ -599,6 +664,14 @@ bool decide_ready(const bm2_ctx *c, const char *who) {
     return true;
 }
 }  // namespace
+
+// The decisions of pairs whose lists lie in HBM (rescue.hip calls this between its gather and its download): see decide_run.
+int bm2h_decide_resident(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *d_hits,
+                         const int64_t *d_off, const int64_t *h_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans, bm2_alnreg_t *out) {
+    if (!decide_ready(c, who)) return BM2_EINVAL;
+    return decide_run(c, who, opt, so, n_pairs, out, h_off, first_pair, pes, plans, d_hits, d_off);
+}
+void bm2h_decide_stats_reset() { g_dc_pairs = 0; g_dc_hits = 0; g_dc_heavy = 0; }
 
 extern "C" void bm2_sam_decide_stats(int64_t *pairs, int64_t *hits, int64_t *pairs_heavy) {
     if (pairs) *pairs = g_dc_pairs.load();

@@ -64,6 +64,38 @@ struct bm2h_decide_scope {
     bm2_ctx *one; bm2h_text_ctxs tc; bm2h_decide_hook hook;
     bm2h_decide_scope(bm2_ctx *const *ctx, int n);
 };
+// The rescue results of one chunk applied to its lists (bm2_pe_rescue_apply_dev's arguments after the context, with the results of the
+// rescue batch beside the tasks: res[t] belongs to tasks[t]; out_cap >= hits + tasks).  Set through bm2h_rescue_hook for the calling
+// thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_RESCUE, bm2h_sam_pe calls it once with the chunk's alnregs, numbers its hits
+// through it (pad = index + 1) and walks only the redo pairs on the host.  0 = success.
+typedef int (*bm2h_rescue_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                                    const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], const bm2_rescue_task_t *tasks,
+                                    const bm2_ksw_result *res, const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off,
+                                    int32_t *redo, int64_t first_pair, bm2_pairplan_t *plans);
+struct bm2h_rescue_hook {
+    bm2h_rescue_hook(bm2h_rescue_batch_fn fn, void *user);
+    ~bm2h_rescue_hook();
+};
+// grouped by pair, strictly ascending in (end, j, r), end / j / r in range for the pair's lists (bm2h_check_hit_off has passed)
+int bm2h_check_rescue_tasks(const char *who, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                            const bm2_rescue_task_t *tasks, const int64_t *task_off);
+void bm2h_rescue_stats_reset();
+void bm2h_rescue_stats_add(long long pairs, long long tasks, long long added, long long redone);
+// The device's hook (rescue.hip; user = bm2h_text_ctxs: contiguous parts of the pairs, one context and host thread per part) and its scope
+int bm2h_dev_rescue_apply_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                                const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], const bm2_rescue_task_t *tasks,
+                                const bm2_ksw_result *res, const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off,
+                                int32_t *redo, int64_t first_pair, bm2_pairplan_t *plans);
+// plans != NULL (BM2_SAM_F_DEVICE_DECIDE as well): the pairs' decisions are taken on the grown lists where they lie in HBM (decide.hip's
+// kernels, packed and permuted on the device) and `out` receives the DECIDED lists; the lists cross the bus once each way.  A redo pair's
+// lists and plan are then of no use: the caller rescues and decides it from its input.
+int bm2h_decide_resident(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *d_hits,
+                         const int64_t *d_off, const int64_t *h_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans, bm2_alnreg_t *out);
+void bm2h_decide_stats_reset();
+struct bm2h_rescue_scope {
+    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_rescue_hook hook;
+    bm2h_rescue_scope(bm2_ctx *const *ctx, int n);
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -180,6 +180,7 @@ extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     if (!c || !c->has_index || !c->ix.ref_string) { bm2_set_error("bm2_sam_pe_dev: the context holds no index"); return BM2_EINVAL; }
     bm2h_text_scope text(&c, 1);
     bm2h_decide_scope decide(&c, 1);
+    bm2h_rescue_scope rescue(&c, 1);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, dev_rescue_batch, c,
                        bm2_dev_cigar_batch, c);
 }
@@ -263,6 +264,7 @@ extern "C" int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     MultiCtx m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
     bm2h_decide_scope decide(ctxs, n_ctx);
+    bm2h_rescue_scope rescue(ctxs, n_ctx);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, multi_rescue_batch, &m, multi_cigar_batch, &m);
 }
 extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,

@@ -356,6 +356,8 @@ thread_local bm2h_text_batch_fn t_text_fn = nullptr;            // the calling t
 thread_local void *t_text_user = nullptr;
 thread_local bm2h_decide_batch_fn t_decide_fn = nullptr;        // the calling thread's hook (bm2h_decide_hook)
 thread_local void *t_decide_user = nullptr;
+thread_local bm2h_rescue_batch_fn t_rescue_fn = nullptr;        // the calling thread's hook (bm2h_rescue_hook)
+thread_local void *t_rescue_user = nullptr;
 
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
 int reg2aln_band(const bm2_opt *opt, int qb, int qe, int64_t rb, int64_t re, int truesc, int w_hit) {
@@ -1043,10 +1045,14 @@ bool fetch_range(const Ref &R, const int32_t *ann_len, int64_t *beg, int64_t mid
 // rescue_apply = what the result does to the mate's hit list.  matesw() strings them together per anchor as the reference does.
 struct RescueTask {                 // one (anchor, direction) alignment of a pair, enumerated before the pair is processed
     int32_t pair, j;                // j = rank of the anchor in b[end] (mem_sam_pe's candidate list)
-    uint8_t end, r;                 // end = which read the ANCHOR belongs to (the mate is !end); r = direction 0..3
+    int32_t end, r;                 // end = which read the ANCHOR belongs to (the mate is !end); r = direction 0..3
     int64_t rb, re;                 // the window, already clamped to the contig
     KswResult res;
+    int32_t pad = 0;
 };
+// (the layout of bm2_rescue_task_t: the tail's tasks go to bm2_pe_rescue_apply_dev's kernels as they are)
+static_assert(sizeof(KswResult) == sizeof(bm2_ksw_result) && sizeof(RescueTask) == sizeof(bm2_rescue_task_t) && offsetof(RescueTask, rb) == offsetof(bm2_rescue_task_t, rb) &&
+              offsetof(RescueTask, res) == offsetof(bm2_rescue_task_t, res) && offsetof(RescueTask, end) == offsetof(bm2_rescue_task_t, end), "RescueTask mirrors bm2_rescue_task_t");
 struct RescueStats { std::atomic<long long> planned{0}, used{0}, missed{0}; };
 
 bool rescue_window(const bm2_opt *opt, const Ref &R, const int32_t *ann_len, const PeStat pes[4], const bm2_alnreg_t *a, int l_ms, int r,
@@ -1208,7 +1214,7 @@ void rescue_plan(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const 
                 if (skip[r]) continue;
                 RescueTask t;
                 if (!rescue_window(opt, R, ann_len, pes, &b[j], l_seq[!i], r, &t.rb, &t.re)) continue;
-                t.pair = pair; t.end = (uint8_t)i; t.r = (uint8_t)r; t.j = (int32_t)j;
+                t.pair = pair; t.end = i; t.r = r; t.j = (int32_t)j;
                 out.push_back(t);
             }
         }
@@ -1318,6 +1324,44 @@ void pe_rescue(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const in
                 matesw(opt, so, R, ann_len, pes, &b[i][j], s[!i].l_seq, s[!i].seq, a[!i], pre ? pre + t : nullptr, t1 - t, st);
             }
     }
+}
+// pe_rescue without an aligner (bm2_pe_rescue_apply; the oracle of rescue.hip): every open direction takes its planned task, window and
+// result, from pre[].  false = a direction is open, has a valid window and no task: the caller redoes the pair with pe_rescue (the
+// lists are then in an intermediate state and of no use).  *added counts the hits inserted.
+bool matesw_planned(const bm2_opt *opt, const Ref &R, const int32_t *ann_len, const PeStat pes[4], const bm2_alnreg_t *a, int l_ms, HitList &ma,
+                    const RescueTask *pre, int n_pre, int *added) {
+    int skip[4], n = 0;
+    rescue_skip(R, pes, a, ma, skip);
+    if (skip[0] + skip[1] + skip[2] + skip[3] == 4) return true;
+    for (int r = 0; r < 4; ++r) {
+        if (skip[r]) continue;
+        const RescueTask *hit = nullptr;
+        for (int t = 0; t < n_pre; ++t) if (pre[t].r == r) { hit = &pre[t]; break; }
+        if (hit) {
+            const int before = ma.n;
+            rescue_apply(opt, R, a, l_ms, r, hit->rb, hit->res, ma);
+            *added += ma.n - before; ++n;
+        } else {
+            int64_t rb, re;
+            if (rescue_window(opt, R, ann_len, pes, a, l_ms, r, &rb, &re)) return false;
+        }
+        if (n) dedup_rescued(opt, ma);
+    }
+    return true;
+}
+bool pe_rescue_planned(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const int32_t *ann_len, const PeStat pes[4], const int l_seq[2],
+                       HitList a[2], const RescueTask *pre, int n_pre, int *added) {
+    static thread_local std::vector<bm2_alnreg_t> b[2];
+    for (int i = 0; i < 2; ++i) rescue_anchors(so, a[i], b[i]);
+    int t = 0;
+    for (int i = 0; i < 2; ++i)
+        for (size_t j = 0; j < b[i].size() && (int)j < so->max_matesw; ++j) {
+            while (t < n_pre && (pre[t].end < i || (pre[t].end == i && pre[t].j < (int)j))) ++t;
+            int t1 = t;
+            while (t1 < n_pre && pre[t1].end == i && pre[t1].j == (int)j) ++t1;
+            if (!matesw_planned(opt, R, ann_len, pes, &b[i][j], l_seq[!i], a[!i], pre + t, t1 - t, added)) return false;
+        }
+    return true;
 }
 void pe_decide_marked(const bm2_opt *opt, const bm2_sam_opt *so, const Ref &R, const PeStat pes[4], uint64_t id, HitList a[2], PairPlan &P) {
     int o, subo, n_sub;
@@ -1620,6 +1664,8 @@ bm2h_text_hook::bm2h_text_hook(bm2h_text_batch_fn fn, void *user) { t_text_fn = 
 bm2h_text_hook::~bm2h_text_hook() { t_text_fn = nullptr; t_text_user = nullptr; }
 bm2h_decide_hook::bm2h_decide_hook(bm2h_decide_batch_fn fn, void *user) { t_decide_fn = fn; t_decide_user = user; }
 bm2h_decide_hook::~bm2h_decide_hook() { t_decide_fn = nullptr; t_decide_user = nullptr; }
+bm2h_rescue_hook::bm2h_rescue_hook(bm2h_rescue_batch_fn fn, void *user) { t_rescue_fn = fn; t_rescue_user = user; }
+bm2h_rescue_hook::~bm2h_rescue_hook() { t_rescue_fn = nullptr; t_rescue_user = nullptr; }
 
 int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) {
     if (hit_off[0] < 0) { bm2_set_error("%s: hit_off[0] is negative", who); return BM2_EINVAL; }
@@ -1657,6 +1703,182 @@ extern "C" int bm2_pe_decide(const bm2_index_desc *idx, const bm2_opt *opt, cons
                 o.extra_flag = P.extra_flag; o.paired = P.paired ? 1 : 0;
             }
     });
+    return BM2_OK;
+}
+
+// ---- mate-rescue results applied to a batch of pairs: the plan, the host form (the oracle of rescue.hip), the counters of both forms
+namespace {
+std::atomic<long long> g_rs_pairs{0}, g_rs_tasks{0}, g_rs_added{0}, g_rs_redone{0};
+void pes_of(const bm2_pestat in[4], PeStat pes[4]) {
+    for (int d = 0; d < 4; ++d) { pes[d].low = in[d].low; pes[d].high = in[d].high; pes[d].failed = in[d].failed; pes[d].avg = in[d].avg; pes[d].std = in[d].std; }
+}
+}  // namespace
+void bm2h_rescue_stats_reset() { g_rs_pairs = 0; g_rs_tasks = 0; g_rs_added = 0; g_rs_redone = 0; }
+void bm2h_rescue_stats_add(long long pairs, long long tasks, long long added, long long redone) { g_rs_pairs += pairs; g_rs_tasks += tasks; g_rs_added += added; g_rs_redone += redone; }
+extern "C" void bm2_sam_rescue_apply_stats(int64_t *pairs, int64_t *tasks, int64_t *hits_added, int64_t *pairs_redone) {
+    if (pairs) *pairs = g_rs_pairs.load();
+    if (tasks) *tasks = g_rs_tasks.load();
+    if (hits_added) *hits_added = g_rs_added.load();
+    if (pairs_redone) *pairs_redone = g_rs_redone.load();
+}
+
+int bm2h_check_rescue_tasks(const char *who, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                            const bm2_rescue_task_t *tasks, const int64_t *task_off) {
+    int rc = bm2h_check_hit_off(who, n_pairs, hit_off);
+    if (rc) return rc;
+    if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("%s: bad argument", who); return BM2_EINVAL; }
+    if (task_off[0] < 0) { bm2_set_error("%s: task_off[0] is negative", who); return BM2_EINVAL; }
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        if (task_off[p + 1] < task_off[p]) { bm2_set_error("%s: task_off decreases at pair %lld", who, (long long)p); return BM2_EINVAL; }
+        if (task_off[p + 1] - task_off[p] > 0x3fffffff) { bm2_set_error("%s: pair %lld has too many tasks", who, (long long)p); return BM2_EINVAL; }
+    }
+    if (task_off[n_pairs] > task_off[0] && !tasks) { bm2_set_error("%s: bad argument", who); return BM2_EINVAL; }
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        if (task_off[p + 1] == task_off[p]) continue;
+        int n_anchor[2];
+        for (int i = 0; i < 2; ++i) {
+            const bm2_alnreg_t *a = hits + hit_off[2 * p + i];
+            const int64_t n = hit_off[2 * p + i + 1] - hit_off[2 * p + i];
+            int k = 0;
+            for (int64_t j = 0; j < n; ++j) k += a[j].score >= a[0].score - so->pen_unpaired;
+            n_anchor[i] = k < so->max_matesw ? k : so->max_matesw;
+        }
+        for (int64_t t = task_off[p]; t < task_off[p + 1]; ++t) {
+            const bm2_rescue_task_t &T = tasks[t];
+            if (T.pair != p) { bm2_set_error("%s: task %lld lies among the tasks of pair %lld and names pair %d (tasks are grouped by pair)", who, (long long)t, (long long)p, T.pair); return BM2_EINVAL; }
+            if (T.end < 0 || T.end > 1 || T.r < 0 || T.r > 3 || T.j < 0 || T.j >= n_anchor[T.end]) {
+                bm2_set_error("%s: task %lld of pair %lld is out of range (end %d, j %d, r %d; %d / %d anchors)", who, (long long)t, (long long)p, T.end, T.j, T.r, n_anchor[0], n_anchor[1]);
+                return BM2_EINVAL;
+            }
+            if (t > task_off[p]) {
+                const bm2_rescue_task_t &U = tasks[t - 1];
+                if (!(U.end < T.end || (U.end == T.end && (U.j < T.j || (U.j == T.j && U.r < T.r))))) {
+                    bm2_set_error("%s: task %lld of pair %lld is not after its predecessor in (end, j, r) order", who, (long long)t, (long long)p); return BM2_EINVAL;
+                }
+            }
+        }
+    }
+    return BM2_OK;
+}
+
+extern "C" int bm2_pe_rescue_plan(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                                  const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes_in[4], bm2_rescue_task_t *tasks, int64_t cap,
+                                  int64_t *task_off, int64_t *n_out) {
+    if (!idx || !opt || !so || n_pairs < 0 || !hit_off || !pes_in || !task_off || !n_out || cap < 0 || (cap > 0 && !tasks) || (n_pairs > 0 && !read_len) ||
+        !idx->ann_offset || !idx->ann_len) { bm2_set_error("bm2_pe_rescue_plan: bad argument"); return BM2_EINVAL; }
+    int rc = bm2h_check_hit_off("bm2_pe_rescue_plan", n_pairs, hit_off);
+    if (rc) return rc;
+    if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("bm2_pe_rescue_plan: bad argument"); return BM2_EINVAL; }
+    Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
+    PeStat pes[4];
+    pes_of(pes_in, pes);
+    int nt = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
+    const int blk = 256, n_blk = (n_pairs + blk - 1) / blk;
+    if (nt > n_blk) nt = n_blk;
+    if (nt < 1) nt = 1;
+    std::vector<std::vector<RescueTask>> part((size_t)n_blk);
+    std::atomic<int> next(0);
+    run_threads(nt, [&]() {
+        for (int b; (b = next.fetch_add(1)) < n_blk;)
+            for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+                const int l_seq[2] = { read_len[2 * pi], read_len[2 * pi + 1] };
+                const HitList a[2] = { view_of(hits, hit_off, 2 * pi), view_of(hits, hit_off, 2 * pi + 1) };
+                rescue_plan(opt, so, R, idx->ann_len, pes, pi, l_seq, a, part[(size_t)b]);
+            }
+    });
+    int64_t g = 0;
+    for (int b = 0; b < n_blk; ++b) {
+        const std::vector<RescueTask> &v = part[(size_t)b];
+        size_t k = 0;
+        for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+            task_off[pi] = g;
+            for (; k < v.size() && v[k].pair == pi; ++k, ++g) {
+                if (g >= cap) continue;
+                bm2_rescue_task_t &o = tasks[g];
+                memset(&o, 0, sizeof o);
+                o.pair = v[k].pair; o.j = v[k].j; o.end = v[k].end; o.r = v[k].r; o.rb = v[k].rb; o.re = v[k].re;
+            }
+        }
+    }
+    task_off[n_pairs] = g;
+    *n_out = g;
+    if (g > cap) { bm2_set_error("bm2_pe_rescue_plan: %lld tasks, room for %lld", (long long)g, (long long)cap); return BM2_ECAP; }
+    return BM2_OK;
+}
+
+extern "C" int bm2_pe_rescue_apply(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                                   const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes_in[4], const bm2_rescue_task_t *tasks,
+                                   const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off, int32_t *redo, int64_t *n_out) {
+    if (!idx || !opt || !so || n_pairs < 0 || !hit_off || !task_off || !pes_in || !n_out || !out_off || out_cap < 0 || (out_cap > 0 && !out) ||
+        (n_pairs > 0 && (!read_len || !redo)) || !idx->ann_offset || !idx->ann_len) { bm2_set_error("bm2_pe_rescue_apply: bad argument"); return BM2_EINVAL; }
+    int rc = bm2h_check_rescue_tasks("bm2_pe_rescue_apply", so, n_pairs, hits, hit_off, tasks, task_off);
+    if (rc) return rc;
+    bm2h_rescue_stats_reset();
+    Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
+    PeStat pes[4];
+    pes_of(pes_in, pes);
+    const RescueTask *const T = reinterpret_cast<const RescueTask *>(tasks);
+    // every pair works in a slice of its own, sized by its hits and tasks (a task adds one hit at most): no list ever outgrows it
+    const int64_t hb = hit_off[0], tb = task_off[0];
+    std::vector<bm2_alnreg_t> work((size_t)((hit_off[2 * (int64_t)n_pairs] - hb) + (task_off[n_pairs] - tb)) + 1);
+    std::vector<int32_t> cnt((size_t)(2 * (int64_t)n_pairs) + 1, 0);
+    std::atomic<long long> added_all(0), redone(0);
+    int nt = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
+    const int blk = 256, n_blk = (n_pairs + blk - 1) / blk;
+    if (nt > n_blk) nt = n_blk;
+    if (nt < 1) nt = 1;
+    std::atomic<int> next(0);
+    auto slice = [&](int64_t pi, int i, int *cap) {               // where list i of pair pi works, and its room
+        const int64_t t0 = task_off[pi], t1 = task_off[pi + 1];
+        int e[2] = { 0, 0 };
+        for (int64_t t = t0; t < t1; ++t) ++e[tasks[t].end ? 0 : 1];
+        const int n0 = (int)(hit_off[2 * pi + 1] - hit_off[2 * pi]), n1 = (int)(hit_off[2 * pi + 2] - hit_off[2 * pi + 1]);
+        *cap = (i ? n1 : n0) + e[i];
+        return work.data() + (hit_off[2 * pi] - hb) + (t0 - tb) + (i ? n0 + e[0] : 0);
+    };
+    run_threads(nt, [&]() {
+        long long my_added = 0, my_redone = 0;
+        for (int b; (b = next.fetch_add(1)) < n_blk;)
+            for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+                HitList a[2];
+                for (int i = 0; i < 2; ++i) {
+                    const HitList v = view_of(hits, hit_off, 2 * pi + i);
+                    a[i].p = slice(pi, i, &a[i].cap); a[i].n = v.n;
+                    if (v.n) memcpy(a[i].p, v.p, sizeof(bm2_alnreg_t) * (size_t)v.n);
+                }
+                const int l_seq[2] = { read_len[2 * pi], read_len[2 * pi + 1] };
+                int added = 0;
+                redo[pi] = 0;
+                const int n_pre = (int)(task_off[pi + 1] - task_off[pi]);
+                if (n_pre && !pe_rescue_planned(opt, so, R, idx->ann_len, pes, l_seq, a, T + task_off[pi], n_pre, &added)) {
+                    redo[pi] = 1; ++my_redone; added = 0;
+                    for (int i = 0; i < 2; ++i) {                  // as the lists came
+                        const HitList v = view_of(hits, hit_off, 2 * pi + i);
+                        a[i].p = slice(pi, i, &a[i].cap); a[i].n = v.n;
+                        if (v.n) memcpy(a[i].p, v.p, sizeof(bm2_alnreg_t) * (size_t)v.n);
+                    }
+                }
+                for (int i = 0; i < 2; ++i) {
+                    int cap;
+                    bm2_alnreg_t *home = slice(pi, i, &cap);
+                    if (a[i].p != home && a[i].n) memmove(home, a[i].p, sizeof(bm2_alnreg_t) * (size_t)a[i].n);     // (a list that moved to the spill arena all the same)
+                    cnt[(size_t)(2 * pi + i)] = a[i].n;
+                }
+                my_added += added;
+            }
+        added_all += my_added; redone += my_redone;
+    });
+    out_off[0] = 0;
+    for (int64_t i = 0; i < 2 * (int64_t)n_pairs; ++i) out_off[i + 1] = out_off[i] + cnt[(size_t)i];
+    *n_out = out_off[2 * (int64_t)n_pairs];
+    if (*n_out > out_cap) { bm2_set_error("bm2_pe_rescue_apply: the lists hold %lld hits, the output has room for %lld", (long long)*n_out, (long long)out_cap); return BM2_ECAP; }
+    for (int64_t pi = 0; pi < n_pairs; ++pi)
+        for (int i = 0; i < 2; ++i) {
+            int cap;
+            const bm2_alnreg_t *home = slice(pi, i, &cap);
+            if (cnt[(size_t)(2 * pi + i)]) memcpy(out + out_off[2 * pi + i], home, sizeof(bm2_alnreg_t) * (size_t)cnt[(size_t)(2 * pi + i)]);
+        }
+    bm2h_rescue_stats_add(n_pairs, task_off[n_pairs] - tb, added_all.load(), redone.load());
     return BM2_OK;
 }
 
@@ -1795,6 +2017,11 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     }
     if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_DECIDE) && (!t_decide_fn || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_DECIDE needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_RESCUE) {
+        if (!t_rescue_fn || !fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_RESCUE needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+        if ((so->flag & F_NO_RESCUE) || so->rescue_inline) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_RESCUE applies the results of the rescue batch: not with MEM_F_NO_RESCUE or rescue_inline"); return BM2_EINVAL; }
+    }
+    const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0;
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
     if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_sam_pe: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
@@ -1878,8 +2105,8 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
             }
         });
         for (int b = 0; b < n_blk; ++b) { base[(size_t)b + 1] += base[(size_t)b]; qbase[(size_t)b + 1] += qbase[(size_t)b]; cbase[(size_t)b + 1] += cbase[(size_t)b]; }
-        if (W.store.size() < (size_t)cbase[(size_t)n_blk] + 1) W.store.resize((size_t)cbase[(size_t)n_blk] + 1);
-        fill_store(cbase, blk, n_blk, n_threads);
+        if (!dev_rescue && W.store.size() < (size_t)cbase[(size_t)n_blk] + 1) W.store.resize((size_t)cbase[(size_t)n_blk] + 1);
+        if (!dev_rescue) fill_store(cbase, blk, n_blk, n_threads);       // (with the bit the lists come back from the hook)
         const long long tot = (long long)base[(size_t)n_blk];
         const int64_t qb_tot = qbase[(size_t)n_blk];
         prof.mark("rescue plan");
@@ -1924,7 +2151,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
             if (rc) return rc;
             prof.mark("rescue batch");
             std::atomic<long long> nr(0);
-            run_threads((long long)n_threads < tot / 8192 + 1 ? n_threads : (int)(tot / 8192 + 1), [&]() {
+            if (!dev_rescue) run_threads((long long)n_threads < tot / 8192 + 1 ? n_threads : (int)(tot / 8192 + 1), [&]() {
                 for (long long t0; (t0 = nr.fetch_add(8192)) < tot;)
                     for (long long t = t0; t < tot && t < t0 + 8192; ++t) {
                         const bm2_ksw_result &r = W.res[(size_t)t];
@@ -1970,6 +2197,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         const RescueTask *pre = batch ? tasks.data() + task_off[(size_t)pi] : nullptr;
         const int n_pre = batch ? (int)(task_off[(size_t)pi + 1] - task_off[(size_t)pi]) : 0;
         t_scratch.reset(); spill_sync(epoch);
+        if (dev_rescue) { pe_decide_marked(opt, so, R, pes, (uint64_t)((n_processed >> 1) + pi), lists + 2 * pi, P); return; }      // (rescued by the hook, or as a redo pair)
         pe_decide(opt, so, R, idx->ann_len, pes, (uint64_t)((n_processed >> 1) + pi), io, lists + 2 * pi, pre, n_pre, batch ? &g_rescue : nullptr, P);
     };
     auto rescue_only = [&](int pi) {                              // the first half of `decide` (BM2_SAM_F_DEVICE_DECIDE: the second runs as a batch)
@@ -1988,9 +2216,70 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     static thread_local CgMemo memo_of_this_thread;              // (kept from chunk to chunk, like W)
     CgMemo &memo = memo_of_this_thread;
     prof.mark("rescue results");
-    g_cigar.planned = 0; g_cigar.used = 0; g_cigar.missed = 0;
+    // BM2_SAM_F_DEVICE_RESCUE: the lists of every pair from one call of the hook (the chunk's hits, numbered on the way, the tasks and
+    // the batch's results as they lie); only the pairs that come back with redo are walked here, with their results copied in first.
+    static thread_local std::vector<bm2_alnreg_t> grown_of_this_thread;
+    static thread_local std::vector<int64_t> grown_off_of_this_thread;
+    static thread_local std::vector<int32_t> redo_of_this_thread;
+    std::vector<bm2_alnreg_t> &grown = grown_of_this_thread;
+    std::vector<int64_t> &grown_off = grown_off_of_this_thread;
+    // with BM2_SAM_F_DEVICE_DECIDE as well the same call decides the pairs on the device: the lists come back decided, with their plans
+    const bool both_dev = dev_rescue && cfn && (so->flag & BM2_SAM_F_DEVICE_DECIDE);
+    static thread_local std::vector<bm2_pairplan_t> dplans_both_of_this_thread;
+    std::vector<bm2_pairplan_t> &dplans = dplans_both_of_this_thread;
+    if (both_dev && dplans.size() < (size_t)n_pairs + 1) dplans.resize((size_t)n_pairs + 1);
     static thread_local std::vector<PairPlan> plans_of_this_thread;      // (kept from chunk to chunk)
     std::vector<PairPlan> &plans = plans_of_this_thread;
+    if (cfn && plans.size() < (size_t)n_pairs) plans.resize((size_t)n_pairs);
+    if (dev_rescue) {
+        std::vector<int32_t> &redo = redo_of_this_thread;
+        const int64_t tot = task_off[(size_t)n_pairs], room = (reg_off[n] - reg_off[0]) + tot;
+        if (grown.size() < (size_t)room + 1) grown.resize((size_t)room + 1);
+        if (grown_off.size() < (size_t)n + 1) grown_off.resize((size_t)n + 1);
+        if (redo.size() < (size_t)n_pairs + 1) redo.resize((size_t)n_pairs + 1);
+        bm2_pestat pq[4];
+        for (int d = 0; d < 4; ++d) { pq[d].low = pes[d].low; pq[d].high = pes[d].high; pq[d].failed = pes[d].failed; pq[d].pad = 0; pq[d].avg = pes[d].avg; pq[d].std = pes[d].std; }
+        const int rc = t_rescue_fn(t_rescue_user, opt, so, n_pairs, alnregs, reg_off, reads->len, pq, reinterpret_cast<const bm2_rescue_task_t *>(tasks.data()),
+                                   tot > 0 ? W.res.data() : nullptr, task_off.data(), grown.data(), room, grown_off.data(), redo.data(),
+                                   n_processed >> 1, both_dev ? dplans.data() : nullptr);
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) { HitList &L = lists[i]; L.p = grown.data() + grown_off[(size_t)i]; L.n = L.cap = (int)(grown_off[(size_t)i + 1] - grown_off[(size_t)i]); }
+        prof.mark("rescue apply (device)");
+        // (redo pairs are the flow's `missed` pairs: at most one in a hundred planned alignments on the inputs the suite pins, a handful per
+        //  chunk in practice, so they are walked here one after the other and not on the pool)
+        for (int pi = 0; pi < n_pairs; ++pi) {
+            if (!redo[(size_t)pi]) continue;
+            for (int64_t t = task_off[(size_t)pi]; t < task_off[(size_t)pi + 1]; ++t) {
+                const bm2_ksw_result &r = W.res[(size_t)t];
+                KswResult &o = tasks[(size_t)t].res;
+                o.score = r.score; o.te = r.te; o.qe = r.qe; o.score2 = r.score2; o.te2 = r.te2; o.tb = r.tb; o.qb = r.qb;
+            }
+            if (both_dev) {                                      // the device decided the pair's lists unrescued: start again from the input
+                spill_sync(epoch);
+                for (int i = 2 * pi; i < 2 * pi + 2; ++i) {
+                    HitList &L = lists[i];
+                    const int k = (int)(reg_off[i + 1] - reg_off[i]);
+                    L.p = nullptr; L.n = L.cap = 0;
+                    L.room(k + 1);
+                    if (k) memcpy(L.p, alnregs + reg_off[i], sizeof(bm2_alnreg_t) * (size_t)k);
+                    for (int h = 0; h < k; ++h) L.p[h].pad = (int32_t)(reg_off[i] + h + 1);
+                    L.n = k;
+                }
+            }
+            rescue_only(pi);                                     // (a list that grows moves to this thread's spill arena)
+            if (both_dev) { t_scratch.reset(); pe_decide_marked(opt, so, R, pes, (uint64_t)((n_processed >> 1) + pi), lists + 2 * pi, plans[(size_t)pi]); }
+        }
+        if (both_dev)
+            for (int pi = 0; pi < n_pairs; ++pi) {
+                if (redo[(size_t)pi]) continue;
+                PairPlan &P = plans[(size_t)pi]; const bm2_pairplan_t &o = dplans[(size_t)pi];
+                for (int k = 0; k < 2; ++k) { P.z[k] = o.z[k]; P.n_pri[k] = o.n_pri[k]; P.q_se[k] = o.q_se[k]; }
+                P.extra_flag = o.extra_flag; P.paired = o.paired != 0;
+            }
+        flush_tallies();
+        prof.mark("rescue redo");
+    }
+    g_cigar.planned = 0; g_cigar.used = 0; g_cigar.missed = 0;
     if (cfn) {                                                   // CIGAR session: decide every pair, note the hits its text will ask for, batch; then print
         int n_threads = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
         if (n_threads < 1) n_threads = 1;
@@ -1999,7 +2288,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         std::vector<std::vector<int32_t>> recs((size_t)n_blk);
         std::atomic<int> next(0), failed(-1);
         const bool dev_decide = (so->flag & BM2_SAM_F_DEVICE_DECIDE) != 0;
-        if (dev_decide) {                                        // rescue on the host threads, then every pair's decisions in one call of the hook
+        if (dev_decide && !both_dev) {                                        // rescue on the host threads, then every pair's decisions in one call of the hook (with the rescue bit as well: decided already)
             run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
                 for (int b; (b = next.fetch_add(1)) < n_blk;)
                     for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) rescue_only(pi);
@@ -2093,6 +2382,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     }
     if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_DECIDE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_DECIDE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_RESCUE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_RESCUE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);

@@ -389,6 +389,48 @@ int bm2_pe_decide_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int
  * form (more than 16 hits in all). */
 void bm2_sam_decide_stats(int64_t *pairs, int64_t *hits, int64_t *pairs_heavy);
 
+/* ---- mate-rescue results applied on the device (rescue.hip): what mem_sam_pe's mem_matesw calls (bwamem_pair.cpp:150-283, :371-376)
+ * do to a pair's two hit lists once the alignments they ask for are known.  A task is one planned (anchor, direction) alignment:
+ * `end` = the read the anchor belongs to (the mate, !end, is the read that is aligned), j = the anchor's rank among that end's
+ * candidates (hits within pen_unpaired of the best, at most max_matesw), r = direction 0..3, [rb, re) = the window clamped to the
+ * anchor's contig, res = what ksw_align2 answered there for the mate as direction r reads it.
+ * bm2_pe_rescue_plan (host only) lists the tasks of a batch of pairs, judged on the lists as they stand, in (pair, end, j, r) order;
+ * tasks of pair p = [task_off[p], task_off[p + 1]); res is zeroed.  *n_out = tasks needed; BM2_ECAP when cap is smaller (task_off is
+ * complete even then).  Lists and offsets as for bm2_pe_decide; read_len[2 n_pairs] = the reads' lengths.
+ * bm2_pe_rescue_apply (host; the oracle) and bm2_pe_rescue_apply_dev (l_pac and the contigs from the context: BM2_EINVAL for one
+ * created without an index) take the same lists and the tasks with their results and write the grown lists to `out`: list i =
+ * out[out_off[i], out_off[i + 1]), out_off from 0 with 2 n_pairs + 1 entries; *n_out = hits needed, BM2_ECAP when out_cap is smaller
+ * (hits + tasks always suffices).  Per pair the result is what mem_sam_pe's rescue loop leaves: anchors from the lists as they came,
+ * end 0 then end 1, directions 0..3, each direction re-judged on the mate's current list, a result inserted in front of the first
+ * hit that scores less, mem_sort_dedup_patch (without a query: nothing merges) after every open direction once the anchor has
+ * applied one; every field travels with its hit, n_comp = 1 as the de-duplication sets it.  The window of a task is taken from the
+ * task.  No alignment runs in either form: when a direction is open, has a valid window and NO task (the mate's list lost the hit
+ * that served it at planning time), redo[p] = 1 and the pair's lists are returned as they came -- the caller runs that pair through
+ * the aligning code.  A pair without any task is copied through unjudged (the plan gives a pair no task when nothing is open).
+ * Tasks must be grouped by pair and strictly ascending in (end, j, r) with end, j, r in range: BM2_EINVAL. */
+typedef struct { int32_t pair, j, end, r; int64_t rb, re; bm2_ksw_result res; int32_t pad; } bm2_rescue_task_t;      /* 64 B */
+#ifdef __cplusplus
+static_assert(sizeof(bm2_rescue_task_t) == 64, "bm2_rescue_task_t is 64 bytes (mirrored by bm2.py)");
+#endif
+int bm2_pe_rescue_plan(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                       const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], bm2_rescue_task_t *tasks, int64_t cap,
+                       int64_t *task_off, int64_t *n_out);
+int bm2_pe_rescue_apply(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                        const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], const bm2_rescue_task_t *tasks,
+                        const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off, int32_t *redo, int64_t *n_out);
+int bm2_pe_rescue_apply_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                            const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], const bm2_rescue_task_t *tasks,
+                            const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off, int32_t *redo, int64_t *n_out);
+/* A library-private bit of bm2_sam_opt.flag, alone or with BM2_SAM_F_DEVICE_DECIDE and / or BM2_SAM_F_DEVICE_TEXT: bm2_sam_pe_dev and
+ * bm2_sam_pe_dev_multi hand the rescue batch's results to bm2_pe_rescue_apply_dev's kernels on their context(s) in one call instead
+ * of walking the pairs on the host; redo pairs go through the host code.  With BM2_SAM_F_DEVICE_DECIDE as well the grown lists stay
+ * on the device, the decide kernels run on them there and the decided lists come down once.  Same bytes.  Off by default.  bm2_sam_pe, the single-end
+ * entry points and calls with MEM_F_NO_RESCUE or rescue_inline answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_RESCUE 0x04000000
+/* What the last rescue-apply call on this process (either form, or the tail with the bit) worked on: pairs, tasks, rescued hits
+ * inserted into the lists, and the pairs that came back with redo. */
+void bm2_sam_rescue_apply_stats(int64_t *pairs, int64_t *tasks, int64_t *hits_added, int64_t *pairs_redone);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

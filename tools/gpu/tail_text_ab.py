@@ -8,6 +8,8 @@ that library (the parent commit's build) and times its bit-off path on the same 
     python tools/gpu/tail_text_ab.py --out profiles/sam_text_dev_ab.json [--parent-lib PATH] [--pairs 500000] [--genome-mbp 3100] [--calls 10]
 --bit text|decide|both: which opt-in bit the "on" variant sets (BM2_SAM_F_DEVICE_TEXT, BM2_SAM_F_DEVICE_DECIDE: the pairs' decisions from
 bm2_pe_decide_dev, or the two together); with decide the result also holds bm2_sam_decide_stats and the bytes the decisions move.
+--bit rescue|rescue+decide|all: BM2_SAM_F_DEVICE_RESCUE (the mate-rescue results applied by bm2_pe_rescue_apply_dev's kernels) alone, with
+the decide bit, with both others; the result then holds bm2_sam_rescue_apply_stats and the bytes the lists and tasks move.
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -99,7 +101,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all"))
     a = ap.parse_args()
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
@@ -124,7 +126,9 @@ def main():
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
-    bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if a.bit in ("text", "both") else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if a.bit in ("decide", "both") else 0)
+    bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if a.bit in ("text", "both", "all") else 0) | \
+           (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if a.bit in ("decide", "both", "rescue+decide", "all") else 0) | \
+           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if a.bit in ("rescue", "rescue+decide", "all") else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
@@ -135,7 +139,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided = None, None, None
+    counters, first, decided, rescued = None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -145,10 +149,12 @@ def main():
                 txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, True, out=bufs[v].a)
             dt, dc = time.perf_counter() - t0, cpu_s() - c0
             texts[v] = txt
-            if v == "on" and a.bit != "decide":
+            if v == "on" and a.bit in ("text", "both", "all"):
                 counters = bm2.sam_text_stats()
-            if v == "on" and a.bit != "text":
+            if v == "on" and a.bit in ("decide", "both", "rescue+decide", "all"):
                 decided = bm2.sam_decide_stats()
+            if v == "on" and a.bit in ("rescue", "rescue+decide", "all"):
+                rescued = bm2.sam_rescue_apply_stats() + bm2.sam_rescue_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -170,6 +176,12 @@ def main():
         mine["decide_stats"] = {"pairs": pairs, "hits": hits, "pairs_heavy": heavy}
         mine["decide_pcie"] = {"up": 56 * hits + 8 * (2 * pairs + 1), "down": 32 * hits + 32 * pairs,
                                "up_per_pair": (56 * hits + 16 * pairs) / max(pairs, 1), "down_per_pair": (32 * hits + 32 * pairs) / max(pairs, 1)}
+    if rescued is not None:                                      # (rescue.hip: 96 B a hit, 64 + 28 B a task, 8 B a list, 12 B a pair up; 96 B a hit, 8 B a list, 8 B a pair down)
+        pairs, tasks, added, redone, planned, used, missed = rescued
+        n_hits = int(aln_off[-1])
+        mine["rescue_stats"] = {"pairs": pairs, "tasks": tasks, "hits_added": added, "pairs_redone": redone, "planned": planned, "missed_in_redo": missed}
+        mine["rescue_pcie"] = {"up": 96 * n_hits + 92 * tasks + 8 * (2 * pairs + 1) + 8 * (pairs + 1) + 8 * pairs + 4 * pairs,
+                               "down_at_most": 96 * (n_hits + added) + 8 * (2 * pairs + 1) + 8 * pairs}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

@@ -67,6 +67,9 @@ SAM_F_DEVICE_DECIDE = 0x02000000    # BM2_SAM_F_DEVICE_DECIDE: sam_pe with a con
 SAM_F_DEVICE_RESCUE = 0x04000000    # BM2_SAM_F_DEVICE_RESCUE: sam_pe with a context applies the mate-rescue results on the device (off by default)
 
 
+SAM_F_DEVICE_PLAN = 0x08000000      # BM2_SAM_F_DEVICE_PLAN: sam_pe with a context plans mate rescue and makes its queries on the device (off by default)
+
+
 class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
     _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
@@ -138,7 +141,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_batch_upload", "bm2_batch_run", "bm2_batch_stats", "bm2_batch_download", "bm2_batch_kernel_ms", "bm2_batch_parts",
            "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats",
            "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats",
-           "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats"]
+           "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats",
+           "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats"]
 
 _lib = None
 
@@ -512,6 +516,14 @@ class Context:
             _chk(rc, "bm2_sam_pe_dev" if paired else "bm2_sam_se_dev")
             return buf[:need.value]                              # a uint8 view of the buffer the library wrote into (no copy); bytes(x) / x.tobytes() for text
 
+    def pe_rescue_plan(self, opt, sam_opt, hits, hit_off, read_len, pes, cap=None):
+        """bm2_pe_rescue_plan_dev: see pe_rescue_plan()."""
+        return pe_rescue_plan(None, opt, sam_opt, hits, hit_off, read_len, pes, ctx=self, cap=cap)
+
+    def pe_rescue_queries(self, enc, off, ln, tasks, cap=None):
+        """bm2_pe_rescue_queries_dev: see pe_rescue_queries()."""
+        return pe_rescue_queries(enc, off, ln, tasks, ctx=self, cap=cap)
+
     def pe_rescue_apply(self, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off):
         """bm2_pe_rescue_apply_dev: see pe_rescue_apply()."""
         return pe_rescue_apply(None, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off, ctx=self)
@@ -716,9 +728,22 @@ def sam_rescue_apply_stats():
     return tuple(x.value for x in v)
 
 
-def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes):
-    """The mate-rescue alignments mem_sam_pe may ask for in a batch of pairs, judged on the lists as they stand (bm2_pe_rescue_plan,
-    host only) -> (a RESCUE_TASK_DT array in (pair, end, j, r) order with zeroed results, task_off[n_pairs + 1])."""
+def sam_rescue_plan_stats():
+    """(pairs, tasks, query_bytes): pairs and tasks of the last device plan (Context.pe_rescue_plan, or a tail with SAM_F_DEVICE_PLAN) and
+    the query bytes made since (by that tail, or by pe_rescue_queries in either form)."""
+    v = [C.c_int64(0) for _ in range(3)]
+    L = lib()
+    L.bm2_sam_rescue_plan_stats.restype = None
+    L.bm2_sam_rescue_plan_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, ctx=None, cap=None):
+    """The mate-rescue alignments mem_sam_pe may ask for in a batch of pairs, judged on the lists as they stand (bm2_pe_rescue_plan;
+    with ctx = a Context holding the index: bm2_pe_rescue_plan_dev, the same on the device)
+    -> (a RESCUE_TASK_DT array in (pair, end, j, r) order with zeroed results, task_off[n_pairs + 1]).
+    cap = a number: ONE call with room for `cap` tasks -> (rc, the `cap` task slots as the call left them, task_off, n_out), nothing raised
+    for BM2_ECAP."""
     L = lib()
     hit_off = np.ascontiguousarray(hit_off, np.int64)
     n_pairs = (len(hit_off) - 1) // 2
@@ -728,17 +753,62 @@ def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes):
     so = sam_opt if sam_opt is not None else default_sam_opt()
     task_off = np.zeros(n_pairs + 1, np.int64)
     need = C.c_int64(0)
-    cap = 0
-    with _DescOf(index_prefix) as d:
-        while True:
+
+    def call(d, tasks, room):
+        tail = (C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data), C.c_void_p(ln.ctypes.data), pq,
+                C.c_void_p(tasks.ctypes.data), C.c_int64(room), C.c_void_p(task_off.ctypes.data), C.byref(need))
+        if ctx is not None:
+            return L.bm2_pe_rescue_plan_dev(C.c_void_p(ctx.h), *tail), "bm2_pe_rescue_plan_dev"
+        return L.bm2_pe_rescue_plan(C.byref(d), *tail), "bm2_pe_rescue_plan"
+
+    def run(d):
+        if cap is not None:
             tasks = np.zeros(max(cap, 1), RESCUE_TASK_DT)
-            rc = L.bm2_pe_rescue_plan(C.byref(d), C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data),
-                                      C.c_void_p(ln.ctypes.data), pq, C.c_void_p(tasks.ctypes.data), C.c_int64(cap), C.c_void_p(task_off.ctypes.data), C.byref(need))
-            if rc == BM2_ECAP:
-                cap = need.value
+            rc, who = call(d, tasks, cap)
+            if rc not in (BM2_OK, BM2_ECAP):
+                _chk(rc, who)
+            return rc, tasks[:cap], task_off, need.value
+        room = 0
+        while True:
+            tasks = np.zeros(max(room, 1), RESCUE_TASK_DT)
+            rc, who = call(d, tasks, room)
+            if rc == BM2_ECAP and need.value > room:
+                room = need.value
                 continue
-            _chk(rc, "bm2_pe_rescue_plan")
+            _chk(rc, who)
             return tasks[:need.value], task_off
+    if ctx is not None:
+        return run(None)
+    with _DescOf(index_prefix) as d:
+        return run(d)
+
+
+def pe_rescue_queries(enc, off, ln, tasks, ctx=None, cap=None):
+    """The oriented queries of a task list (bm2_pe_rescue_queries; with ctx: bm2_pe_rescue_queries_dev, made on the device): query t =
+    read 2 * pair + !end as direction r reads it -> (the queries back to back as a uint8 array, q_off[n_tasks + 1]).
+    cap = a number: ONE call with room for `cap` bytes -> (rc, the buffer, q_off, n_out), nothing raised for BM2_ECAP."""
+    L = lib()
+    reads, keep = _reads_struct(enc, off, ln)
+    t = np.ascontiguousarray(tasks, RESCUE_TASK_DT)
+    q_off = np.zeros(len(t) + 1, np.int64)
+    need = C.c_int64(0)
+
+    def call(out, room):
+        tail = (C.byref(reads), C.c_int64(len(t)), C.c_void_p(t.ctypes.data), C.c_void_p(out.ctypes.data), C.c_int64(room), C.c_void_p(q_off.ctypes.data), C.byref(need))
+        if ctx is not None:
+            return L.bm2_pe_rescue_queries_dev(C.c_void_p(ctx.h), *tail), "bm2_pe_rescue_queries_dev"
+        return L.bm2_pe_rescue_queries(*tail), "bm2_pe_rescue_queries"
+    if cap is not None:
+        out = np.full(max(cap, 1), 0xee, np.uint8)
+        rc, who = call(out, cap)
+        if rc not in (BM2_OK, BM2_ECAP):
+            _chk(rc, who)
+        return rc, out[:cap], q_off, need.value
+    room = int(np.asarray(ln, np.int64)[2 * t["pair"] + 1 - t["end"]].sum()) if len(t) and (t["pair"] >= 0).all() and (2 * t["pair"].astype(np.int64) + 1 < len(ln)).all() and ((t["end"] == 0) | (t["end"] == 1)).all() else 0
+    out = np.full(max(room, 1), 0xee, np.uint8)
+    rc, who = call(out, room)
+    _chk(rc, who)
+    return out[:need.value], q_off
 
 
 def pe_rescue_apply(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, tasks, task_off, ctx=None):

@@ -42,6 +42,9 @@ struct bm2_ctx {
     DevBuf b_dc_in, b_dc_out, b_dc_work, b_dc_scan, b_dc_scan2, b_dc_pack, b_dc_final;      // (the last two: the resident form)
     // workspaces of bm2_pe_rescue_apply_dev (rescue.hip): lists + tasks + offsets, the pairs' working slices, the grown lists, a scan
     DevBuf b_rs_in, b_rs_work, b_rs_out, b_rs_scan;
+    // workspaces of bm2_pe_rescue_plan_dev / bm2_pe_rescue_queries_dev (plan.hip): lists + offsets, or the mates' codes + the queries'
+    // descriptors; counts + places; the tasks, or the queries of the record-level call; a scan
+    DevBuf b_pl_in, b_pl_work, b_pl_out, b_pl_scan;
     void *txt_pin = nullptr; size_t txt_pin_cap = 0;             // page-locked staging of the packed names / qualities
     // the host array whose copy b_ref holds since the CIGAR batch of the SAM tail call in progress (NULL: none); the text of the same call reads it there
     const void *tail_enc = nullptr; size_t tail_enc_bytes = 0;

@@ -96,6 +96,37 @@ struct bm2h_rescue_scope {
     bm2_ctx *one; bm2h_text_ctxs tc; bm2h_rescue_hook hook;
     bm2h_rescue_scope(bm2_ctx *const *ctx, int n);
 };
+// The plan of one chunk's mate rescue (bm2_pe_rescue_plan_dev's arguments after the context; the tasks go to what room(arg, n) answers
+// once their number is known, task_off[n_pairs + 1] and *n_out are filled), and the rescue batch with its queries made where it runs:
+// the flat arrays of bm2h_ksw_batch_fn without qbuf -- query i is the mate of tasks[i] as its direction reads it, q_off[n] = their bytes.
+// Set through bm2h_plan_hook for the calling thread; when they are set AND so->flag has BM2_SAM_F_DEVICE_PLAN, bm2h_sam_pe walks no pair
+// to plan and copies no mate: it sizes its lists from the tasks and describes the batch from task fields and read lengths.  0 = success.
+typedef int (*bm2h_plan_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                                  const int32_t *read_len, const bm2_pestat pes[4], bm2_rescue_task_t *(*room)(void *arg, int64_t n), void *arg,
+                                  int64_t *task_off, int64_t *n_out);
+typedef int (*bm2h_ksw_resident_fn)(void *user, int32_t n, const bm2_rescue_task_t *tasks, const bm2_reads *reads, const int64_t *q_off, const int32_t *q_len,
+                                    const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, bm2_ksw_result *out);
+struct bm2h_plan_hook {
+    bm2h_plan_hook(bm2h_plan_batch_fn fn, bm2h_ksw_resident_fn qfn, void *user);
+    ~bm2h_plan_hook();
+};
+int bm2h_plan_query_offsets(const char *who, const bm2_reads *reads, int64_t n_tasks, const bm2_rescue_task_t *tasks, const uint8_t *out, int64_t cap,
+                            int64_t *q_off, int64_t *n_out);
+void bm2h_plan_stats_set(long long pairs, long long tasks, long long query_bytes);
+void bm2h_plan_stats_add_query_bytes(long long query_bytes);
+// The device's hooks (plan.hip, matesw.hip; user = bm2h_text_ctxs: contiguous parts of the pairs / of the tasks, one context and host
+// thread per part) and their scope.  bm2h_plan_queries_resident: the queries of tasks [0, n) into d_out (device memory) at
+// q_off[t] - q_off[0], from the run of the reads' codes that holds their mates, uploaded here; asynchronous on the context's stream.
+int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                        const int32_t *read_len, const bm2_pestat pes[4], bm2_rescue_task_t *(*room)(void *arg, int64_t n), void *arg,
+                        int64_t *task_off, int64_t *n_out);
+int bm2h_dev_rescue_batch_resident(void *user, int32_t n, const bm2_rescue_task_t *tasks, const bm2_reads *reads, const int64_t *q_off, const int32_t *q_len,
+                                   const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, bm2_ksw_result *out);
+int bm2h_plan_queries_resident(bm2_ctx *c, const bm2_reads *reads, int64_t n, const bm2_rescue_task_t *tasks, const int64_t *q_off, uint8_t *d_out);
+struct bm2h_plan_scope {
+    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_plan_hook hook;
+    bm2h_plan_scope(bm2_ctx *const *ctx, int n);
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -53,10 +53,16 @@ k_ksw_align2_reg(const uint8_t *__restrict__ qbase, RefPtr tbase, const KswTask 
 
 // Runs n tasks: queries at qbase_host[q_off[i]] (uploaded here), targets at t_off[i] either in the same uploaded buffer
 // (d_tbase == NULL) or in a device-resident array (d_tbase, e.g. the context's ref_string replica).
+// The resident form (made != NULL, qbuf == NULL): no query comes from the host.  The queries are those of made->tasks[0, n), built in
+// HBM from the reads' codes (plan.hip: bm2h_plan_queries_resident) where the uploaded buffer would lie; q_off may start anywhere (a part
+// of a larger batch) and q_off[n] is read; qbuf_bytes is not.
+struct KswMade { const bm2_reads *reads; const bm2_rescue_task_t *tasks; };
 static int ksw_batch_run(bm2_ctx *c, int32_t n, const uint8_t *qbuf, int64_t qbuf_bytes, const RefPtr *d_tbase, const int64_t *q_off,
                          const int32_t *q_len, const int64_t *t_off, const int32_t *t_len, const int32_t *xtra, const int8_t mat[25], int o_del,
-                         int e_del, int o_ins, int e_ins, bm2_ksw_result *out) {
+                         int e_del, int o_ins, int e_ins, bm2_ksw_result *out, const KswMade *made = nullptr) {
     if (n == 0) return BM2_OK;
+    const int64_t q_base = made ? q_off[0] : 0;
+    if (made) qbuf_bytes = q_off[n] - q_base;
     int rc = bm2_check(hipSetDevice(c->device), "hipSetDevice");
     if (rc) return rc;
     TailProf prof("ksw_batch");
@@ -93,7 +99,7 @@ static int ksw_batch_run(bm2_ctx *c, int32_t n, const uint8_t *qbuf, int64_t qbu
         int64_t at = nb_of[(size_t)(lo / grain)];
         for (int64_t i = lo; i < hi; ++i) {
             KswTask &T = tasks[(size_t)i];
-            T.q_off = q_off[i]; T.t_off = t_off[i]; T.qlen = q_len[i]; T.tlen = t_len[i]; T.xtra = xtra[i]; T.pad = 0;
+            T.q_off = q_off[i] - q_base; T.t_off = t_off[i]; T.qlen = q_len[i]; T.tlen = t_len[i]; T.xtra = xtra[i]; T.pad = 0;
             T.b_off = at; at += (t_len[i] + 1) / 2 + 1;
         }
     });
@@ -127,7 +133,11 @@ static int ksw_batch_run(bm2_ctx *c, int32_t n, const uint8_t *qbuf, int64_t qbu
     hipStream_t s = c->stream;
     KswTask *d_task = (KswTask *)b_task.p;
     int *d_order = (int *)((char *)b_task.p + ((task_bytes + 15) & ~(size_t)15));
-    rc = bm2_copy_h2d(c, b_seq.p, qbuf, (size_t)qbuf_bytes);       // (pageable memory: through the context's pinned staging buffers)
+    if (made) {
+        rc = bm2h_plan_queries_resident(c, made->reads, n, made->tasks, q_off, (uint8_t *)b_seq.p);
+        if (!rc && prof.on) { (void)hipStreamSynchronize(s); prof.mark("rescue queries (device)"); }
+        if (!rc) bm2h_plan_stats_add_query_bytes(qbuf_bytes);
+    } else rc = bm2_copy_h2d(c, b_seq.p, qbuf, (size_t)qbuf_bytes);       // (pageable memory: through the context's pinned staging buffers)
     if (!rc) rc = bm2_copy_h2d(c, d_task, tasks.data(), task_bytes);
     if (!rc) rc = bm2_copy_h2d(c, d_order, order.data(), ord_bytes);
     if (rc) return rc;
@@ -174,6 +184,42 @@ static int dev_rescue_batch(void *user, int32_t n, const uint8_t *qbuf, int64_t 
                          opt->o_ins, opt->e_ins, out);
 }
 
+// The same with the queries made on the device (BM2_SAM_F_DEVICE_PLAN; bm2h_ksw_resident_fn, user = bm2h_text_ctxs): the tasks cut into
+// contiguous parts as multi_rescue_batch cuts them, every part building the queries of its own tasks.  Tasks are in pair order, so a
+// part's mates are a contiguous run of reads: that run is what the part uploads.
+int bm2h_dev_rescue_batch_resident(void *user, int32_t n, const bm2_rescue_task_t *tasks, const bm2_reads *reads, const int64_t *q_off, const int32_t *q_len,
+                                   const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, bm2_ksw_result *out) {
+    const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
+    const int64_t part_min = bm2_knob("BM2_KSW_PART", 8192);             // tasks that are worth a context of their own (launch policy)
+    int G = (int)((int64_t)n / (part_min > 0 ? part_min : 1) + 1 < m->n ? (int64_t)n / (part_min > 0 ? part_min : 1) + 1 : m->n);
+    if (G < 1) G = 1;
+    auto part = [&](int g) {
+        const int64_t lo = (int64_t)n * g / G, hi = (int64_t)n * (g + 1) / G;
+        bm2_ctx *c = m->ctx[g];
+        const RefPtr ref = c->ix.ref(0);
+        const KswMade made = { reads, tasks + lo };
+        return ksw_batch_run(c, (int32_t)(hi - lo), nullptr, 0, &ref, q_off + lo, q_len + lo, t_pos + lo, t_len + lo, xtra + lo, opt->mat, opt->o_del, opt->e_del,
+                             opt->o_ins, opt->e_ins, out + lo, &made);
+    };
+    if (G == 1) return part(0);
+    std::vector<int> rcs((size_t)G, 0);
+    std::vector<std::string> msgs((size_t)G);
+    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
+    auto one = [&](int g) {
+        bm2_host_thread_budget() = budget;
+        rcs[(size_t)g] = part(g);
+        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
+    };
+    const int mine = bm2_host_thread_budget();
+    std::vector<std::thread> th;
+    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
+    one(0);
+    for (auto &t : th) t.join();
+    bm2_host_thread_budget() = mine;
+    for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("context %d: %s", g, msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
+    return BM2_OK;
+}
+
 extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,
                               const bm2_read_text *txt, const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed,
                               const bm2_pestat *pes_in, bm2_pestat *pes_out, char *out, int64_t cap, int64_t *n_out) {
@@ -181,6 +227,7 @@ extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     bm2h_text_scope text(&c, 1);
     bm2h_decide_scope decide(&c, 1);
     bm2h_rescue_scope rescue(&c, 1);
+    bm2h_plan_scope plan(&c, 1);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, dev_rescue_batch, c,
                        bm2_dev_cigar_batch, c);
 }
@@ -265,6 +312,7 @@ extern "C" int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     bm2h_text_scope text(ctxs, n_ctx);
     bm2h_decide_scope decide(ctxs, n_ctx);
     bm2h_rescue_scope rescue(ctxs, n_ctx);
+    bm2h_plan_scope plan(ctxs, n_ctx);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, multi_rescue_batch, &m, multi_cigar_batch, &m);
 }
 extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,

@@ -30,6 +30,7 @@
 #include "host_pool.h"
 #include "pipeline.h"
 #include "ksort_dev.h"
+#include "rescue_dev.h"                 /* rs_infer_dir, rs_pos2rid, rs_window: shared with plan.hip */
 
 #pragma clang fp contract(off)      /* mask_level_redun * min rounds as in sam_tail.cpp's object code; holds to the end of the file */
 
@@ -60,50 +61,6 @@ struct RsByScore {
 };
 static __device__ __attribute__((noinline)) void rs_sort_by_end(int n, int32_t *ord, const bm2_alnreg_t *A) { RsByEnd lt = { A }; k_introsort_flat(n, ord, lt); }
 static __device__ __attribute__((noinline)) void rs_sort_by_score(int n, int32_t *ord, const bm2_alnreg_t *A) { RsByScore lt = { A }; k_introsort_flat(n, ord, lt); }
-
-static __device__ __forceinline__ int rs_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist) {      // bwamem_pair.cpp:58-65
-    const int r1 = (b1 >= l_pac), r2 = (b2 >= l_pac);
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-static __device__ int rs_pos2rid(const RsPrm &P, int64_t pos_f) {                         // bntseq.cpp:378-392
-    if (pos_f >= P.l_pac) return -1;
-    int left = 0, mid = 0, right = P.n_seqs;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= P.ann_off[mid]) {
-            if (mid == P.n_seqs - 1) break;
-            if (pos_f < P.ann_off[mid + 1]) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
-}
-// Is there a window for direction r of this anchor (rescue_window of sam_tail.cpp: bwamem_pair.cpp:176-186 with bns_fetch_seq's clamp)?
-static __device__ bool rs_window(const RsPrm &P, int64_t a_rb, int a_rid, int l_ms, int r) {
-    const int is_rev = (r >> 1 != (r & 1)), is_larger = !(r >> 1);
-    int64_t rb, re;
-    if (!is_rev) {
-        rb = is_larger ? a_rb + P.low[r] : a_rb - P.high[r];
-        re = (is_larger ? a_rb + P.high[r] : a_rb - P.low[r]) + l_ms;
-    } else {
-        rb = (is_larger ? a_rb + P.low[r] : a_rb - P.high[r]) - l_ms;
-        re = is_larger ? a_rb + P.high[r] : a_rb - P.low[r];
-    }
-    if (rb < 0) rb = 0;
-    if (re > P.l_pac << 1) re = P.l_pac << 1;
-    if (rb >= re) return false;
-    const int64_t mid = (rb + re) >> 1;
-    const int rev = mid >= P.l_pac;
-    const int rid = rs_pos2rid(P, rev ? (P.l_pac << 1) - 1 - mid : mid);
-    if (rid < 0) return false;
-    int64_t far_beg = P.ann_off[rid], far_end = far_beg + P.ann_len[rid];
-    if (rev) { const int64_t t = far_beg; far_beg = (P.l_pac << 1) - far_end; far_end = (P.l_pac << 1) - t; }
-    rb = rb > far_beg ? rb : far_beg;
-    re = re < far_end ? re : far_end;
-    return a_rid == rid && re - rb >= P.min_seed_len;
-}
 
 struct RsList { bm2_alnreg_t *pool; int32_t *L; int n, used, cap; };         // hits pool[0, used), the list = pool[L[0 .. n)]
 
@@ -208,7 +165,7 @@ static __device__ bool rs_pair(const RsPrm &P, int64_t p, int *n_added) {
                         for (int x = M.n; x > at; --x) M.L[x] = M.L[x - 1];
                         M.pool[M.used] = h; M.L[at] = M.used; ++M.used; ++M.n; ++added;
                     }
-                } else if (rs_window(P, a_rb, a_rid, l_ms, r)) return false;
+                } else { int64_t wb, we; if (rs_window(P, a_rb, a_rid, l_ms, r, &wb, &we)) return false; }
                 if (n) rs_dedup(P, M, ord, keep, gone);
             }
         }

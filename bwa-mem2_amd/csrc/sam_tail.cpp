@@ -358,6 +358,9 @@ thread_local bm2h_decide_batch_fn t_decide_fn = nullptr;        // the calling t
 thread_local void *t_decide_user = nullptr;
 thread_local bm2h_rescue_batch_fn t_rescue_fn = nullptr;        // the calling thread's hook (bm2h_rescue_hook)
 thread_local void *t_rescue_user = nullptr;
+thread_local bm2h_plan_batch_fn t_plan_fn = nullptr;            // the calling thread's hooks (bm2h_plan_hook): the plan, and the rescue batch with
+thread_local bm2h_ksw_resident_fn t_planq_fn = nullptr;         // its queries made on the device
+thread_local void *t_plan_user = nullptr;
 
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
 int reg2aln_band(const bm2_opt *opt, int qb, int qe, int64_t rb, int64_t re, int truesc, int w_hit) {
@@ -1666,6 +1669,8 @@ bm2h_decide_hook::bm2h_decide_hook(bm2h_decide_batch_fn fn, void *user) { t_deci
 bm2h_decide_hook::~bm2h_decide_hook() { t_decide_fn = nullptr; t_decide_user = nullptr; }
 bm2h_rescue_hook::bm2h_rescue_hook(bm2h_rescue_batch_fn fn, void *user) { t_rescue_fn = fn; t_rescue_user = user; }
 bm2h_rescue_hook::~bm2h_rescue_hook() { t_rescue_fn = nullptr; t_rescue_user = nullptr; }
+bm2h_plan_hook::bm2h_plan_hook(bm2h_plan_batch_fn fn, bm2h_ksw_resident_fn qfn, void *user) { t_plan_fn = fn; t_planq_fn = qfn; t_plan_user = user; }
+bm2h_plan_hook::~bm2h_plan_hook() { t_plan_fn = nullptr; t_planq_fn = nullptr; t_plan_user = nullptr; }
 
 int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) {
     if (hit_off[0] < 0) { bm2_set_error("%s: hit_off[0] is negative", who); return BM2_EINVAL; }
@@ -1709,6 +1714,7 @@ extern "C" int bm2_pe_decide(const bm2_index_desc *idx, const bm2_opt *opt, cons
 // ---- mate-rescue results applied to a batch of pairs: the plan, the host form (the oracle of rescue.hip), the counters of both forms
 namespace {
 std::atomic<long long> g_rs_pairs{0}, g_rs_tasks{0}, g_rs_added{0}, g_rs_redone{0};
+std::atomic<long long> g_pl_pairs{0}, g_pl_tasks{0}, g_pl_qbytes{0};
 void pes_of(const bm2_pestat in[4], PeStat pes[4]) {
     for (int d = 0; d < 4; ++d) { pes[d].low = in[d].low; pes[d].high = in[d].high; pes[d].failed = in[d].failed; pes[d].avg = in[d].avg; pes[d].std = in[d].std; }
 }
@@ -1720,6 +1726,14 @@ extern "C" void bm2_sam_rescue_apply_stats(int64_t *pairs, int64_t *tasks, int64
     if (tasks) *tasks = g_rs_tasks.load();
     if (hits_added) *hits_added = g_rs_added.load();
     if (pairs_redone) *pairs_redone = g_rs_redone.load();
+}
+
+void bm2h_plan_stats_set(long long pairs, long long tasks, long long query_bytes) { g_pl_pairs = pairs; g_pl_tasks = tasks; g_pl_qbytes = query_bytes; }
+void bm2h_plan_stats_add_query_bytes(long long query_bytes) { g_pl_qbytes += query_bytes; }
+extern "C" void bm2_sam_rescue_plan_stats(int64_t *pairs, int64_t *tasks, int64_t *query_bytes) {
+    if (pairs) *pairs = g_pl_pairs.load();
+    if (tasks) *tasks = g_pl_tasks.load();
+    if (query_bytes) *query_bytes = g_pl_qbytes.load();
 }
 
 int bm2h_check_rescue_tasks(const char *who, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
@@ -1803,6 +1817,54 @@ extern "C" int bm2_pe_rescue_plan(const bm2_index_desc *idx, const bm2_opt *opt,
     task_off[n_pairs] = g;
     *n_out = g;
     if (g > cap) { bm2_set_error("bm2_pe_rescue_plan: %lld tasks, room for %lld", (long long)g, (long long)cap); return BM2_ECAP; }
+    return BM2_OK;
+}
+
+// The arguments of the two bm2_pe_rescue_queries forms checked, q_off and *n_out filled; BM2_ECAP when the queries need more than cap
+int bm2h_plan_query_offsets(const char *who, const bm2_reads *reads, int64_t n_tasks, const bm2_rescue_task_t *tasks, const uint8_t *out, int64_t cap,
+                            int64_t *q_off, int64_t *n_out) {
+    if (!reads || n_tasks < 0 || n_tasks > 0x7fffffff || !q_off || !n_out || cap < 0 || (cap > 0 && !out) || (n_tasks > 0 && (!tasks || !reads->enc || !reads->off || !reads->len))) {
+        bm2_set_error("%s: bad argument", who); return BM2_EINVAL;
+    }
+    int64_t at = 0;
+    for (int64_t t = 0; t < n_tasks; ++t) {
+        const bm2_rescue_task_t &T = tasks[t];
+        if (T.pair < 0 || 2 * (int64_t)T.pair + 1 >= reads->n_reads || T.end < 0 || T.end > 1 || T.r < 0 || T.r > 3 || reads->len[2 * T.pair + !T.end] < 0) {
+            bm2_set_error("%s: task %lld is out of range (pair %d, end %d, r %d; %d reads)", who, (long long)t, T.pair, T.end, T.r, reads->n_reads); return BM2_EINVAL;
+        }
+        q_off[t] = at;
+        at += reads->len[2 * T.pair + !T.end];
+    }
+    q_off[n_tasks] = at;
+    *n_out = at;
+    bm2h_plan_stats_set(0, n_tasks, at);
+    if (at > cap) { bm2_set_error("%s: the queries take %lld bytes, room for %lld", who, (long long)at, (long long)cap); return BM2_ECAP; }
+    return BM2_OK;
+}
+
+// queries[q_off[t], q_off[t + 1]) = the mate of task t as direction r reads it (rescue_query), for tasks [lo, hi)
+static void rescue_queries_range(const bm2_reads *reads, const bm2_rescue_task_t *tasks, int64_t lo, int64_t hi, const int64_t *q_off, uint8_t *out) {
+    for (int64_t t = lo; t < hi; ++t) {
+        const bm2_rescue_task_t &T = tasks[t];
+        const int m = 2 * T.pair + !T.end, l_ms = reads->len[m];
+        const uint8_t *ms = reads->enc + reads->off[m];
+        uint8_t *q = out + q_off[t];
+        if (!(T.r >> 1 != (T.r & 1))) memcpy(q, ms, (size_t)l_ms);
+        else for (int i = 0; i < l_ms; ++i) q[l_ms - 1 - i] = ms[i] < 4 ? 3 - ms[i] : 4;
+    }
+}
+
+extern "C" int bm2_pe_rescue_queries(const bm2_reads *reads, int64_t n_tasks, const bm2_rescue_task_t *tasks, uint8_t *out, int64_t cap, int64_t *q_off,
+                                     int64_t *n_out) {
+    const int rc = bm2h_plan_query_offsets("bm2_pe_rescue_queries", reads, n_tasks, tasks, out, cap, q_off, n_out);
+    if (rc) return rc;
+    const int64_t grain = 8192;
+    int nt = bm2_effective_cpus();
+    if (nt > n_tasks / grain + 1) nt = (int)(n_tasks / grain + 1);
+    std::atomic<int64_t> next(0);
+    run_threads(nt < 1 ? 1 : nt, [&]() {
+        for (int64_t lo; (lo = next.fetch_add(grain)) < n_tasks;) rescue_queries_range(reads, tasks, lo, lo + grain < n_tasks ? lo + grain : n_tasks, q_off, out);
+    });
     return BM2_OK;
 }
 
@@ -2021,7 +2083,11 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         if (!t_rescue_fn || !fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_RESCUE needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
         if ((so->flag & F_NO_RESCUE) || so->rescue_inline) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_RESCUE applies the results of the rescue batch: not with MEM_F_NO_RESCUE or rescue_inline"); return BM2_EINVAL; }
     }
-    const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0;
+    if (so->flag & BM2_SAM_F_DEVICE_PLAN) {
+        if (!t_plan_fn || !t_planq_fn || !fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PLAN needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+        if ((so->flag & F_NO_RESCUE) || so->rescue_inline) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PLAN plans the rescue batch: not with MEM_F_NO_RESCUE or rescue_inline"); return BM2_EINVAL; }
+    }
+    const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0, dev_plan = (so->flag & BM2_SAM_F_DEVICE_PLAN) != 0;
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
     if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_sam_pe: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
@@ -2086,6 +2152,10 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         if (n_threads < 1) n_threads = 1;
         const int blk = 256, n_blk = (n_pairs + blk - 1) / blk;
         const int nt_blk = n_threads < n_blk ? n_threads : n_blk;
+        long long tot = 0;
+        int64_t qb_tot = 0;
+        bool flat = false;
+        if (!dev_plan) {
         std::vector<std::vector<RescueTask>> part((size_t)n_blk);
         std::vector<int64_t> base((size_t)n_blk + 1, 0), qbase((size_t)n_blk + 1, 0), cbase((size_t)n_blk + 1, 0);   // tasks / query bytes / hit slots before block b
         std::atomic<int> next(0);
@@ -2107,12 +2177,12 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         for (int b = 0; b < n_blk; ++b) { base[(size_t)b + 1] += base[(size_t)b]; qbase[(size_t)b + 1] += qbase[(size_t)b]; cbase[(size_t)b + 1] += cbase[(size_t)b]; }
         if (!dev_rescue && W.store.size() < (size_t)cbase[(size_t)n_blk] + 1) W.store.resize((size_t)cbase[(size_t)n_blk] + 1);
         if (!dev_rescue) fill_store(cbase, blk, n_blk, n_threads);       // (with the bit the lists come back from the hook)
-        const long long tot = (long long)base[(size_t)n_blk];
-        const int64_t qb_tot = qbase[(size_t)n_blk];
+        tot = (long long)base[(size_t)n_blk];
+        qb_tot = qbase[(size_t)n_blk];
         prof.mark("rescue plan");
         if (tot > 0x7fffffff) { bm2_set_error("bm2_sam_pe: too many rescue alignments in one chunk"); return BM2_EINVAL; }
         g_rescue.planned = tot;
-        const bool flat = fn && tot > 0;
+        flat = fn && tot > 0;
         if (tasks.size() < (size_t)tot) tasks.resize((size_t)tot);
         if (task_off.size() < (size_t)n_pairs + 1) task_off.resize((size_t)n_pairs + 1);
         if (flat) {
@@ -2134,20 +2204,74 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
                         const int m = 2 * pi + !T.end, l_ms = reads->len[m];
                         W.q_off[(size_t)g] = qb; W.q_len[(size_t)g] = l_ms;
                         W.t_pos[(size_t)g] = T.rb; W.t_len[(size_t)g] = (int32_t)(T.re - T.rb); W.xtra[(size_t)g] = rescue_xtra(opt, l_ms);
-                        const uint8_t *ms = reads->enc + reads->off[m];
-                        uint8_t *q = W.qbuf.data() + qb;         // the mate as direction r reads it (rescue_query)
-                        if (!(T.r >> 1 != (T.r & 1))) memcpy(q, ms, (size_t)l_ms);
-                        else for (int i = 0; i < l_ms; ++i) q[l_ms - 1 - i] = ms[i] < 4 ? 3 - ms[i] : 4;
+                        rescue_queries_range(reads, reinterpret_cast<const bm2_rescue_task_t *>(tasks.data()), g, g + 1, W.q_off.data(), W.qbuf.data());      // the mate as direction r reads it
                         qb += l_ms;
                     }
                 }
             }
         });
         task_off[(size_t)n_pairs] = tot;
+        } else {
+        // BM2_SAM_F_DEVICE_PLAN: the tasks from one call of the hook (the chunk's hits, offsets and read lengths go up, the tasks and
+        // task_off come down); the host sizes the store from them and describes the batch with integers alone -- the queries are made
+        // on the device from the reads' codes (the second hook), no byte of a mate is touched here.
+        if (task_off.size() < (size_t)n_pairs + 1) task_off.resize((size_t)n_pairs + 1);
+        bm2_pestat pq[4];
+        for (int d = 0; d < 4; ++d) { pq[d].low = pes[d].low; pq[d].high = pes[d].high; pq[d].failed = pes[d].failed; pq[d].pad = 0; pq[d].avg = pes[d].avg; pq[d].std = pes[d].std; }
+        auto room = [](void *arg, int64_t k) -> bm2_rescue_task_t * {
+            std::vector<RescueTask> &v = *(std::vector<RescueTask> *)arg;
+            if (v.size() < (size_t)k) v.resize((size_t)k);
+            return reinterpret_cast<bm2_rescue_task_t *>(v.data());
+        };
+        int64_t got = 0;
+        const int rc = t_plan_fn(t_plan_user, opt, so, n_pairs, alnregs, reg_off, reads->len, pq, room, &tasks, task_off.data(), &got);
+        if (rc) return rc;
+        tot = got;
+        prof.mark("rescue plan (device)");
+        if (tot > 0x7fffffff) { bm2_set_error("bm2_sam_pe: too many rescue alignments in one chunk"); return BM2_EINVAL; }
+        g_rescue.planned = tot;
+        flat = tot > 0;
+        if (flat && W.q_off.size() < (size_t)tot + 1) { W.q_off.resize((size_t)tot + 1); W.t_pos.resize((size_t)tot + 1); W.q_len.resize((size_t)tot + 1); W.t_len.resize((size_t)tot + 1); W.xtra.resize((size_t)tot + 1); W.res.resize((size_t)tot + 1); }
+        std::vector<int64_t> qbase((size_t)n_blk + 1, 0), cbase((size_t)n_blk + 1, 0);      // query bytes / hit slots before block b
+        std::atomic<int> next(0);
+        run_threads(nt_blk, [&]() {
+            for (int b; (b = next.fetch_add(1)) < n_blk;) {
+                int64_t q = 0, slots = 0;
+                for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+                    extra[2 * pi] = extra[2 * pi + 1] = 0;
+                    for (int64_t t = task_off[(size_t)pi]; t < task_off[(size_t)pi + 1]; ++t) { const int m = 2 * pi + !tasks[(size_t)t].end; q += reads->len[m]; ++extra[m]; }
+                }
+                for (int i = 2 * b * blk; i < n && i < 2 * (b + 1) * blk; ++i) slots += (reg_off[i + 1] - reg_off[i]) + extra[i] + slack;
+                qbase[(size_t)b + 1] = q; cbase[(size_t)b + 1] = slots;
+            }
+        });
+        for (int b = 0; b < n_blk; ++b) { qbase[(size_t)b + 1] += qbase[(size_t)b]; cbase[(size_t)b + 1] += cbase[(size_t)b]; }
+        qb_tot = qbase[(size_t)n_blk];
+        if (!dev_rescue && W.store.size() < (size_t)cbase[(size_t)n_blk] + 1) W.store.resize((size_t)cbase[(size_t)n_blk] + 1);
+        if (!dev_rescue) fill_store(cbase, blk, n_blk, n_threads);
+        next = 0;
+        if (flat) run_threads(nt_blk, [&]() {
+            for (int b; (b = next.fetch_add(1)) < n_blk;) {
+                int64_t qb = qbase[(size_t)b];
+                const int p_end = (b + 1) * blk < n_pairs ? (b + 1) * blk : n_pairs;
+                for (int64_t g = task_off[(size_t)(b * blk)]; g < task_off[(size_t)p_end]; ++g) {
+                    const RescueTask &T = tasks[(size_t)g];
+                    const int l_ms = reads->len[2 * T.pair + !T.end];
+                    W.q_off[(size_t)g] = qb; W.q_len[(size_t)g] = l_ms;
+                    W.t_pos[(size_t)g] = T.rb; W.t_len[(size_t)g] = (int32_t)(T.re - T.rb); W.xtra[(size_t)g] = rescue_xtra(opt, l_ms);
+                    qb += l_ms;
+                }
+            }
+        });
+        if (flat) W.q_off[(size_t)tot] = qb_tot;
+        prof.mark("rescue lists");
+        }
         if (flat) {                                              // one call of the hook
-            prof.mark("rescue flatten");
-            const int rc = fn(user, (int32_t)tot, W.qbuf.data(), qb_tot, W.q_off.data(), W.q_len.data(), W.t_pos.data(), W.t_len.data(), W.xtra.data(), opt,
-                              idx->ref_string, W.res.data());
+            if (!dev_plan) prof.mark("rescue flatten");
+            const int rc = dev_plan ? t_planq_fn(t_plan_user, (int32_t)tot, reinterpret_cast<const bm2_rescue_task_t *>(tasks.data()), reads, W.q_off.data(), W.q_len.data(),
+                                                 W.t_pos.data(), W.t_len.data(), W.xtra.data(), opt, W.res.data())
+                                    : fn(user, (int32_t)tot, W.qbuf.data(), qb_tot, W.q_off.data(), W.q_len.data(), W.t_pos.data(), W.t_len.data(), W.xtra.data(), opt,
+                                         idx->ref_string, W.res.data());
             if (rc) return rc;
             prof.mark("rescue batch");
             std::atomic<long long> nr(0);
@@ -2383,6 +2507,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if ((so->flag & BM2_SAM_F_DEVICE_TEXT) && !t_text_fn) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_TEXT needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_DECIDE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_DECIDE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_RESCUE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_RESCUE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_PLAN) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PLAN is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);

@@ -394,7 +394,7 @@ void bm2_sam_decide_stats(int64_t *pairs, int64_t *hits, int64_t *pairs_heavy);
  * `end` = the read the anchor belongs to (the mate, !end, is the read that is aligned), j = the anchor's rank among that end's
  * candidates (hits within pen_unpaired of the best, at most max_matesw), r = direction 0..3, [rb, re) = the window clamped to the
  * anchor's contig, res = what ksw_align2 answered there for the mate as direction r reads it.
- * bm2_pe_rescue_plan (host only) lists the tasks of a batch of pairs, judged on the lists as they stand, in (pair, end, j, r) order;
+ * bm2_pe_rescue_plan (host; the oracle of bm2_pe_rescue_plan_dev below) lists the tasks of a batch of pairs, judged on the lists as they stand, in (pair, end, j, r) order;
  * tasks of pair p = [task_off[p], task_off[p + 1]); res is zeroed.  *n_out = tasks needed; BM2_ECAP when cap is smaller (task_off is
  * complete even then).  Lists and offsets as for bm2_pe_decide; read_len[2 n_pairs] = the reads' lengths.
  * bm2_pe_rescue_apply (host; the oracle) and bm2_pe_rescue_apply_dev (l_pac and the contigs from the context: BM2_EINVAL for one
@@ -430,6 +430,33 @@ int bm2_pe_rescue_apply_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *s
 /* What the last rescue-apply call on this process (either form, or the tail with the bit) worked on: pairs, tasks, rescued hits
  * inserted into the lists, and the pairs that came back with redo. */
 void bm2_sam_rescue_apply_stats(int64_t *pairs, int64_t *tasks, int64_t *hits_added, int64_t *pairs_redone);
+
+/* ---- mate rescue planned on the device (plan.hip).  bm2_pe_rescue_plan_dev takes the arguments of bm2_pe_rescue_plan after the context
+ * (l_pac and the contigs from the context: BM2_EINVAL for one created without an index) and keeps its contract to the letter: tasks in
+ * (pair, end, j, r) order, j = the anchor's rank among the CANDIDATES (hits with score >= best - pen_unpaired, at most max_matesw), not
+ * its index in the list; res and pad zero, so that a task's 64 bytes equal the host's; task_off complete and *n_out = the tasks needed
+ * even under BM2_ECAP, when the tasks below cap have been written.
+ * bm2_pe_rescue_queries (host: the flatten loop of bm2_sam_pe behind a C name) and bm2_pe_rescue_queries_dev build the oriented queries
+ * of a task list: query t = the mate of task t (read 2 * pair + !end of `reads`) as direction r reads it -- a plain copy when
+ * (r >> 1) == (r & 1), otherwise reversed with c < 4 ? 3 - c : 4 -- written back to back to `out`; q_off[n_tasks + 1] = where each
+ * begins, *n_out = their bytes; BM2_ECAP when cap is smaller (q_off and *n_out are complete, nothing has been written).  Of a task
+ * they read pair, end and r (each checked against the reads: BM2_EINVAL). */
+int bm2_pe_rescue_plan_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                           const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], bm2_rescue_task_t *tasks, int64_t cap,
+                           int64_t *task_off, int64_t *n_out);
+int bm2_pe_rescue_queries(const bm2_reads *reads, int64_t n_tasks, const bm2_rescue_task_t *tasks, uint8_t *out, int64_t cap, int64_t *q_off,
+                          int64_t *n_out);
+int bm2_pe_rescue_queries_dev(bm2_ctx *c, const bm2_reads *reads, int64_t n_tasks, const bm2_rescue_task_t *tasks, uint8_t *out, int64_t cap,
+                              int64_t *q_off, int64_t *n_out);
+/* A library-private bit of bm2_sam_opt.flag, alone or with any of the three bits above: bm2_sam_pe_dev and bm2_sam_pe_dev_multi take the
+ * chunk's rescue tasks from bm2_pe_rescue_plan_dev's kernels on their context(s) (hits, offsets and read lengths go up, tasks and
+ * task_off come down) and run the rescue batch on queries made on the device from the reads' codes: the host walks no pair to plan and
+ * copies no mate.  Same bytes.  Off by default.  bm2_sam_pe, the single-end entry points and calls with MEM_F_NO_RESCUE or rescue_inline
+ * answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_PLAN 0x08000000
+/* pairs and tasks of the last bm2_pe_rescue_plan_dev call on this process (or of the last tail with the bit), and the query bytes made
+ * since: by that tail's rescue batch, or by a bm2_pe_rescue_queries call of either form (which reports no pairs). */
+void bm2_sam_rescue_plan_stats(int64_t *pairs, int64_t *tasks, int64_t *query_bytes);
 
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */

@@ -10,6 +10,9 @@ that library (the parent commit's build) and times its bit-off path on the same 
 bm2_pe_decide_dev, or the two together); with decide the result also holds bm2_sam_decide_stats and the bytes the decisions move.
 --bit rescue|rescue+decide|all: BM2_SAM_F_DEVICE_RESCUE (the mate-rescue results applied by bm2_pe_rescue_apply_dev's kernels) alone, with
 the decide bit, with both others; the result then holds bm2_sam_rescue_apply_stats and the bytes the lists and tasks move.
+--bit plan|plan+rescue|plan+rescue+decide+text: BM2_SAM_F_DEVICE_PLAN (mate rescue planned by bm2_pe_rescue_plan_dev's kernels, the rescue
+batch's queries made on the device) alone, with the rescue bit, with all three others; the result then holds bm2_sam_rescue_plan_stats and
+the bytes the plan and the queries move.
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -101,7 +104,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text"))
     a = ap.parse_args()
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
@@ -126,9 +129,9 @@ def main():
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
-    bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if a.bit in ("text", "both", "all") else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if a.bit in ("decide", "both", "rescue+decide", "all") else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if a.bit in ("rescue", "rescue+decide", "all") else 0)
+    on = set({"both": "text+decide", "all": "text+decide+rescue"}.get(a.bit, a.bit).split("+"))
+    bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if "text" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if "decide" in on else 0) | \
+           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
@@ -139,7 +142,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided, rescued = None, None, None, None
+    counters, first, decided, rescued, planned_dev = None, None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -149,12 +152,14 @@ def main():
                 txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, True, out=bufs[v].a)
             dt, dc = time.perf_counter() - t0, cpu_s() - c0
             texts[v] = txt
-            if v == "on" and a.bit in ("text", "both", "all"):
+            if v == "on" and "text" in on:
                 counters = bm2.sam_text_stats()
-            if v == "on" and a.bit in ("decide", "both", "rescue+decide", "all"):
+            if v == "on" and "decide" in on:
                 decided = bm2.sam_decide_stats()
-            if v == "on" and a.bit in ("rescue", "rescue+decide", "all"):
+            if v == "on" and "rescue" in on:
                 rescued = bm2.sam_rescue_apply_stats() + bm2.sam_rescue_stats()
+            if v == "on" and "plan" in on:
+                planned_dev = bm2.sam_rescue_plan_stats() + bm2.sam_rescue_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -182,6 +187,12 @@ def main():
         mine["rescue_stats"] = {"pairs": pairs, "tasks": tasks, "hits_added": added, "pairs_redone": redone, "planned": planned, "missed_in_redo": missed}
         mine["rescue_pcie"] = {"up": 96 * n_hits + 92 * tasks + 8 * (2 * pairs + 1) + 8 * (pairs + 1) + 8 * pairs + 4 * pairs,
                                "down_at_most": 96 * (n_hits + added) + 8 * (2 * pairs + 1) + 8 * pairs}
+    if planned_dev is not None:                                  # (plan.hip: 96 B a hit, 8 B a list offset, 4 B a read length up, 64 B a task and 8 B a pair down; the queries: the
+        pairs, tasks, q_bytes, planned, used, missed = planned_dev      #  mates' run of codes -- at most the chunk's -- and 24 B a task up INSTEAD of the oriented queries)
+        n_hits = int(aln_off[-1])
+        mine["plan_stats"] = {"pairs": pairs, "tasks": tasks, "query_bytes": q_bytes, "planned": planned, "used": used, "missed": missed}
+        mine["plan_pcie"] = {"plan_up": 96 * n_hits + 8 * (2 * pairs + 1) + 4 * 2 * pairs, "plan_down": 64 * tasks + 8 * (pairs + 1),
+                             "queries_up_at_most": int(ch.f.n_bases) + 24 * tasks, "queries_up_without_the_bit": q_bytes}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

@@ -70,6 +70,9 @@ SAM_F_DEVICE_RESCUE = 0x04000000    # BM2_SAM_F_DEVICE_RESCUE: sam_pe with a con
 SAM_F_DEVICE_PLAN = 0x08000000      # BM2_SAM_F_DEVICE_PLAN: sam_pe with a context plans mate rescue and makes its queries on the device (off by default)
 
 
+SAM_F_DEVICE_PESTAT = 0x10000000    # BM2_SAM_F_DEVICE_PESTAT: sam_pe with a context and no model given counts the insert sizes on the device (off by default)
+
+
 class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
     _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
@@ -142,7 +145,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_batch_fetch", "bm2_batch_finish", "bm2_batch_download_alnregs", "bm2_finish_regs_dev", "bm2_chunk_hits_sharded", "bm2_index_build", "bm2_sam_opt_init", "bm2_sam_se", "bm2_sam_pe", "bm2_fastq_parse", "bm2_fastq_parse_mt", "bm2_fastq_free", "bm2_ksw_align2", "bm2_ksw_align2_dev", "bm2_sam_pe_dev", "bm2_sam_se_dev", "bm2_sam_pe_dev_multi", "bm2_sam_se_dev_multi", "bm2_sam_cigar_stats", "bm2_gen_cigar", "bm2_gen_cigar_dev", "bm2_sam_header", "bm2_sam_rescue_stats",
            "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats",
            "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats",
-           "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats"]
+           "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats",
+           "bm2_pe_stat", "bm2_pe_stat_dev", "bm2_sam_pestat_stats"]
 
 _lib = None
 
@@ -520,6 +524,10 @@ class Context:
         """bm2_pe_rescue_plan_dev: see pe_rescue_plan()."""
         return pe_rescue_plan(None, opt, sam_opt, hits, hit_off, read_len, pes, ctx=self, cap=cap)
 
+    def pe_stat(self, opt, sam_opt, hits, hit_off, hist=True, hist_cap=None):
+        """bm2_pe_stat_dev: see pe_stat()."""
+        return pe_stat(None, opt, sam_opt, hits, hit_off, ctx=self, hist=hist, hist_cap=hist_cap)
+
     def pe_rescue_queries(self, enc, off, ln, tasks, cap=None):
         """bm2_pe_rescue_queries_dev: see pe_rescue_queries()."""
         return pe_rescue_queries(enc, off, ln, tasks, ctx=self, cap=cap)
@@ -736,6 +744,53 @@ def sam_rescue_plan_stats():
     L.bm2_sam_rescue_plan_stats.restype = None
     L.bm2_sam_rescue_plan_stats(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def sam_pestat_stats():
+    """(pairs, counted, hit_bytes_up, hit_bytes_shared) of the last device model (Context.pe_stat, or a tail with SAM_F_DEVICE_PESTAT):
+    its pairs, those counted into a bin, the bytes of hits it uploaded, and the bytes of hits the plan of the same tail call found
+    resident and did not send again."""
+    v = [C.c_int64(0) for _ in range(4)]
+    L = lib()
+    L.bm2_sam_pestat_stats.restype = None
+    L.bm2_sam_pestat_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def pe_stat(index_prefix, opt, sam_opt, hits, hit_off, ctx=None, hist=True, hist_cap=None):
+    """The insert-size model of a batch of pairs (bm2_pe_stat; with ctx = a Context holding the index: bm2_pe_stat_dev, the pairs counted
+    on the device) -> (pes: a list of four PeStat, hist: the merged histogram as a uint32 array [4, max(max_ins, 0) + 1]).
+    hist = False: no histogram is asked for -> (pes, None).
+    hist_cap = a number: ONE call with room for `hist_cap` counts -> (rc, pes, the `hist_cap` counts as the call left them), nothing
+    raised for BM2_ECAP."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    n_pairs = (len(hit_off) - 1) // 2
+    a = np.ascontiguousarray(hits, ALNREG_DT)
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    pq = (PeStat * 4)()
+    bins = max(int(so.max_ins), 0) + 1
+    room = 4 * bins if hist_cap is None else int(hist_cap)
+    h = np.full(max(room, 1), 0xeeeeeeee, np.uint32) if hist else None
+
+    def call(d):
+        tail = (C.byref(opt), C.byref(so), C.c_int32(n_pairs), C.c_void_p(a.ctypes.data), C.c_void_p(hit_off.ctypes.data), pq,
+                C.c_void_p(h.ctypes.data if hist else None), C.c_int64(room if hist else 0))
+        if ctx is not None:
+            return L.bm2_pe_stat_dev(C.c_void_p(ctx.h), *tail), "bm2_pe_stat_dev"
+        return L.bm2_pe_stat(C.byref(d), *tail), "bm2_pe_stat"
+    if ctx is not None:
+        rc, who = call(None)
+    else:
+        with _DescOf(index_prefix) as d:
+            rc, who = call(d)
+    pes = [PeStat(x.low, x.high, x.failed, x.pad, x.avg, x.std) for x in pq]
+    if hist_cap is not None:
+        if rc not in (BM2_OK, BM2_ECAP):
+            _chk(rc, who)
+        return rc, pes, (h[:room] if hist else None)
+    _chk(rc, who)
+    return pes, (h[:4 * bins].reshape(4, bins) if hist else None)
 
 
 def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, ctx=None, cap=None):

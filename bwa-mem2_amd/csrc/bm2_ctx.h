@@ -45,6 +45,11 @@ struct bm2_ctx {
     // workspaces of bm2_pe_rescue_plan_dev / bm2_pe_rescue_queries_dev (plan.hip): lists + offsets, or the mates' codes + the queries'
     // descriptors; counts + places; the tasks, or the queries of the record-level call; a scan
     DevBuf b_pl_in, b_pl_work, b_pl_out, b_pl_scan;
+    // What b_pl_in holds since the model's pass of the SAM tail call in progress (pestat.hip), in plan_run's layout: the hits
+    // [hbase, hbase + n_hits) of `hits` at 0 and the 2 * n_pairs + 1 re-based offsets of `hit_off` behind them.  epoch = that call's
+    // number (bm2h_tail_epoch), 0 = nothing.  plan_run sends neither again when its own arguments are these; whatever else writes
+    // b_pl_in clears it.
+    struct PlResident { const void *hits = nullptr, *hit_off = nullptr; int64_t hbase = 0, n_hits = 0; int32_t n_pairs = 0; uint64_t epoch = 0; } pl_res;
     void *txt_pin = nullptr; size_t txt_pin_cap = 0;             // page-locked staging of the packed names / qualities
     // the host array whose copy b_ref holds since the CIGAR batch of the SAM tail call in progress (NULL: none); the text of the same call reads it there
     const void *tail_enc = nullptr; size_t tail_enc_bytes = 0;

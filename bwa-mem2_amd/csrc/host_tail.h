@@ -127,6 +127,35 @@ struct bm2h_plan_scope {
     bm2_ctx *one; bm2h_text_ctxs tc; bm2h_plan_hook hook;
     bm2h_plan_scope(bm2_ctx *const *ctx, int n);
 };
+// The contiguous parts a chunk's pairs are cut into by the hooks that read its hit lists (the plan's and the model's: the same parts, so
+// that what one of them uploads serves the other): knob BM2_PLAN_PART = pairs that are worth a context of their own, at most n_ctx parts;
+// part g = pairs [n_pairs * g / G, n_pairs * (g + 1) / G).
+int bm2h_plan_parts(int64_t n_pairs, int n_ctx);
+// The insert-size model of one chunk (bm2_pe_stat_dev's arguments after the context, without the histogram).  Set through
+// bm2h_pestat_hook for the calling thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_PESTAT AND the caller gave no model,
+// bm2h_sam_pe takes pes[4] from the hook instead of counting the pairs on its threads.  0 = success.
+typedef int (*bm2h_pestat_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                                    bm2_pestat pes[4]);
+struct bm2h_pestat_hook {
+    bm2h_pestat_hook(bm2h_pestat_batch_fn fn, void *user);
+    ~bm2h_pestat_hook();
+};
+// pestat_model of sam_tail.cpp behind a name: the four models read off the merged histogram hist[4][top + 1] (top = max(max_ins, 0))
+void bm2h_pestat_model(const uint32_t *hist, int64_t top, bm2_pestat pes[4]);
+void bm2h_pestat_stats_set(long long pairs, long long counted, long long hit_bytes_up);       // (and no byte shared)
+void bm2h_pestat_stats_shared(long long hit_bytes, bool add);                                 // add = false: set
+// The number of the bm2h_sam_pe call in progress on this thread that took its model from the hook (0: none).  What the model's hook
+// leaves in a context's b_pl_in is tagged with it, and only the plan hook of the same call may find it there.
+uint64_t bm2h_tail_epoch();
+// The device's hook (pestat.hip; user = bm2h_text_ctxs: the parts of bm2h_plan_parts, one context and host thread per part, their
+// histograms summed on the host) and its scope, which also forgets what the contexts hold in b_pl_in when the call ends.
+int bm2h_dev_pestat_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                          bm2_pestat pes[4]);
+struct bm2h_pestat_scope {
+    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_pestat_hook hook;
+    bm2h_pestat_scope(bm2_ctx *const *ctx, int n);
+    ~bm2h_pestat_scope();
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -129,10 +129,11 @@ typedef std::function<bm2_rescue_task_t *(int64_t)> PlRoom;      // room for n t
 
 // The batch on one context.  Offsets may start anywhere (a part of a larger batch); task_off comes back from 0, the tasks name pairs
 // from pair_base on.  The caller has checked the offsets.  *n_out = the tasks the pairs need; min(*n_out, cap) of them are written to
-// what room(min(*n_out, cap)) answers.
+// what room(min(*n_out, cap)) answers.  epoch = the number of the tail call this belongs to when its model was counted on the device
+// (bm2h_tail_epoch; 0: none): the hits and offsets that pass left in b_pl_in are used where they lie when they are exactly these.
 static int plan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
                     const int64_t *hit_off, const int32_t *read_len, const bm2_pestat pes[4], int32_t pair_base, const PlRoom &room, int64_t cap,
-                    int64_t *task_off, int64_t *n_out) {
+                    int64_t *task_off, int64_t *n_out, uint64_t epoch = 0) {
     *n_out = 0;
     task_off[0] = 0;
     if (n_pairs == 0) return BM2_OK;
@@ -140,10 +141,12 @@ static int plan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_s
     if (rc) return rc;
     TailProf prof("pe_plan_dev");
     const int64_t n_lists = 2 * (int64_t)n_pairs, hbase = hit_off[0], n_hits = hit_off[n_lists] - hbase;
-    std::vector<int64_t> hoff((size_t)n_lists + 1);
-    for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hbase;
     const size_t in_b = up256((size_t)n_hits * sizeof(bm2_alnreg_t)), hoff_b = up256((size_t)(n_lists + 1) * 8), len_b = up256((size_t)n_lists * 4);
     const size_t cnt_b = up256((size_t)n_lists * 4), off_b = up256((size_t)(n_lists + 1) * 8), toff_b = up256((size_t)(n_pairs + 1) * 8);
+    const bm2_ctx::PlResident &have = c->pl_res;
+    const bool resident = epoch != 0 && have.epoch == epoch && have.hits == (hits ? (const void *)(hits + hbase) : nullptr) && have.hit_off == (const void *)hit_off &&
+                          have.hbase == hbase && have.n_hits == n_hits && have.n_pairs == n_pairs && c->b_pl_in.cap >= in_b + hoff_b + len_b + 256;
+    c->pl_res.epoch = 0;                                         // (one reader; a miss overwrites the buffer)
     if ((rc = bm2_reserve(c->b_pl_in, in_b + hoff_b + len_b + 256))) return rc;
     if ((rc = bm2_reserve(c->b_pl_work, cnt_b + off_b + toff_b + 256))) return rc;
     PlPrm P;
@@ -159,8 +162,12 @@ static int plan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_s
     P.ann_off = c->ix.ann_offset; P.ann_len = c->ix.ann_len; P.l_pac = c->ix.l_pac; P.n_seqs = c->ix.n_seqs;
     P.n_pairs = n_pairs; P.min_seed_len = opt->min_seed_len; P.pen_unpaired = so->pen_unpaired; P.max_matesw = so->max_matesw; P.pair_base = pair_base;
     for (int k = 0; k < 4; ++k) { P.low[k] = pes[k].low; P.high[k] = pes[k].high; P.failed[k] = pes[k].failed; }
-    if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits + hbase, (size_t)n_hits * sizeof(bm2_alnreg_t)))) return rc;
-    if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
+    if (!resident) {
+        std::vector<int64_t> hoff((size_t)n_lists + 1);
+        for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hbase;
+        if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits + hbase, (size_t)n_hits * sizeof(bm2_alnreg_t)))) return rc;
+        if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
+    } else bm2h_pestat_stats_shared((long long)((size_t)n_hits * sizeof(bm2_alnreg_t)), true);
     if ((rc = bm2_copy_h2d(c, (void *)P.read_len, read_len, (size_t)n_lists * 4))) return rc;
     prof.mark("H2D");
     const dim3 grid((unsigned)((n_lists + 255) / 256)), block(256);
@@ -235,6 +242,7 @@ int bm2h_plan_queries_resident(bm2_ctx *c, const bm2_reads *reads, int64_t n, co
         }
     });
     const size_t enc_b = up256(PL_ENC_FRONT + (size_t)(hi - lo) + PL_ENC_BACK), q_b = up256((size_t)n * sizeof(PlQuery));
+    c->pl_res.epoch = 0;                                         // (b_pl_in changes hands)
     int rc = bm2_reserve(c->b_pl_in, enc_b + q_b + 256);
     if (rc) return rc;
     uint8_t *d_enc = (uint8_t *)c->b_pl_in.p + PL_ENC_FRONT;
@@ -258,6 +266,12 @@ extern "C" int bm2_pe_rescue_queries_dev(bm2_ctx *c, const bm2_reads *reads, int
     return bm2_copy_d2h(c, out, c->b_pl_out.p, (size_t)bytes);       // (waits for the kernel: same stream)
 }
 
+int bm2h_plan_parts(int64_t n_pairs, int n_ctx) {
+    const int64_t part_min = bm2_knob("BM2_PLAN_PART", 65536);           // pairs that are worth a context of their own (launch policy)
+    int G = (int)(n_pairs / (part_min > 0 ? part_min : 1) + 1 < n_ctx ? n_pairs / (part_min > 0 ? part_min : 1) + 1 : n_ctx);
+    return G < 1 ? 1 : G;
+}
+
 // ---- the hook of the SAM tail (bm2h_plan_batch_fn; user = bm2h_text_ctxs): the chunk's pairs cut into contiguous parts, one context
 // and one host thread per part, as the other hooks do.  A pair's tasks depend on its own lists and the chunk's model only.
 int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
@@ -266,12 +280,12 @@ int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, i
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
     for (int g = 0; g < m->n; ++g) if (!plan_ready(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN")) return BM2_EINVAL;
     bm2h_plan_stats_set(0, 0, 0);
-    const int64_t part_min = bm2_knob("BM2_PLAN_PART", 65536);           // pairs that are worth a context of their own (launch policy)
-    int G = (int)(n_pairs / (part_min > 0 ? part_min : 1) + 1 < m->n ? n_pairs / (part_min > 0 ? part_min : 1) + 1 : m->n);
-    if (G < 1) G = 1;
+    bm2h_pestat_stats_shared(0, false);
+    const uint64_t epoch = bm2h_tail_epoch();
+    const int G = bm2h_plan_parts(n_pairs, m->n);
     if (G == 1) {
         const int rc = plan_run(m->ctx[0], "BM2_SAM_F_DEVICE_PLAN", opt, so, n_pairs, hits, hit_off, read_len, pes, 0, [&](int64_t n) { return room(arg, n); },
-                                INT64_MAX, task_off, n_out);
+                                INT64_MAX, task_off, n_out, epoch);
         if (!rc) bm2h_plan_stats_set(n_pairs, *n_out, 0);
         return rc;
     }
@@ -286,7 +300,7 @@ int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, i
         const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
         poff[(size_t)g].resize((size_t)(hi - lo + 1));
         rcs[(size_t)g] = plan_run(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, read_len + 2 * lo, pes, (int32_t)lo,
-                                  [&, g](int64_t n) { part[(size_t)g].resize((size_t)n); return part[(size_t)g].data(); }, INT64_MAX, poff[(size_t)g].data(), &got[(size_t)g]);
+                                  [&, g](int64_t n) { part[(size_t)g].resize((size_t)n); return part[(size_t)g].data(); }, INT64_MAX, poff[(size_t)g].data(), &got[(size_t)g], epoch);
         if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
     };
     const int mine = bm2_host_thread_budget();

@@ -361,6 +361,10 @@ thread_local void *t_rescue_user = nullptr;
 thread_local bm2h_plan_batch_fn t_plan_fn = nullptr;            // the calling thread's hooks (bm2h_plan_hook): the plan, and the rescue batch with
 thread_local bm2h_ksw_resident_fn t_planq_fn = nullptr;         // its queries made on the device
 thread_local void *t_plan_user = nullptr;
+thread_local bm2h_pestat_batch_fn t_pestat_fn = nullptr;        // the calling thread's hook (bm2h_pestat_hook)
+thread_local void *t_pestat_user = nullptr;
+thread_local uint64_t t_tail_epoch = 0;                          // bm2h_tail_epoch()
+std::atomic<uint64_t> g_tail_epoch{0};
 
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
 int reg2aln_band(const bm2_opt *opt, int qb, int qe, int64_t rb, int64_t re, int truesc, int w_hit) {
@@ -970,15 +974,15 @@ int cal_sub(const bm2_opt *opt, const HitList &r) {            // bwamem_pair.cp
 // any order), and everything else is read off the counts: a quartile is a rank in the cumulative counts; the mean sums integers (exact
 // in a double whatever the order); the deviation adds (v - mean)^2 once per pair in ascending order of v, which is the order -- and
 // therefore the rounding -- of the reference's loop over its sorted array.
-void pestat(const bm2_opt *opt, const bm2_sam_opt *so, int64_t l_pac, int n_reads, const bm2_alnreg_t *alnregs, const int64_t *reg_off, PeStat pes[4]) {
-    const int n_pairs = n_reads >> 1;
-    const int64_t top = so->max_ins > 0 ? so->max_ins : 0;       // bins 1 .. max_ins
-    for (int d = 0; d < 4; ++d) pes[d] = PeStat();
+// The counting half: hist[4][top + 1] = the chunk's insert sizes per orientation, summed over the threads (k_pestat of pestat.hip is
+// its device form).  hist comes back sized and filled.
+void pestat_count(const bm2_opt *opt, const bm2_sam_opt *so, int64_t l_pac, int n_pairs, const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t top,
+                  std::vector<uint32_t> &hist) {
     int nt = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
     if (nt > n_pairs / 8192 + 1) nt = n_pairs / 8192 + 1;
     if (nt < 1) nt = 1;
     const size_t bins = (size_t)top + 1;
-    std::vector<uint32_t> hist((size_t)nt * 4 * bins, 0);
+    hist.assign((size_t)nt * 4 * bins, 0);
     std::atomic<int> nx(0), tid(0);
     run_threads(nt, [&]() {
         uint32_t *mine = hist.data() + (size_t)tid.fetch_add(1) * 4 * bins;
@@ -994,10 +998,20 @@ void pestat(const bm2_opt *opt, const bm2_sam_opt *so, int64_t l_pac, int n_read
                 if (is && is <= top) ++mine[(size_t)dir * bins + (size_t)is];
             }
     });
-    uint64_t count[4] = { 0, 0, 0, 0 };
     for (int d = 0; d < 4; ++d) {
         uint32_t *h = hist.data() + (size_t)d * bins;            // thread 0's histogram becomes the total
         for (int t = 1; t < nt; ++t) { const uint32_t *o = hist.data() + ((size_t)t * 4 + d) * bins; for (size_t v = 0; v < bins; ++v) h[v] += o[v]; }
+    }
+    hist.resize(4 * bins);
+}
+// The model half: everything from the merged histogram hist[4][top + 1] on, the `tot < 10` rule and the 5 % rule included.  Double
+// arithmetic in a fixed order, on the host for both forms of the count.
+void pestat_model(const uint32_t *hist, int64_t top, PeStat pes[4]) {
+    const size_t bins = (size_t)top + 1;
+    for (int d = 0; d < 4; ++d) pes[d] = PeStat();
+    uint64_t count[4] = { 0, 0, 0, 0 };
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t *h = hist + (size_t)d * bins;
         uint64_t tot = 0;
         for (size_t v = 0; v < bins; ++v) tot += h[v];
         count[d] = tot;
@@ -1028,6 +1042,12 @@ void pestat(const bm2_opt *opt, const bm2_sam_opt *so, int64_t l_pac, int n_read
     uint64_t mx = 0;
     for (int d = 0; d < 4; ++d) mx = mx > count[d] ? mx : count[d];
     for (int d = 0; d < 4; ++d) if (pes[d].failed == 0 && count[d] < mx * 0.05) pes[d].failed = 1;
+}
+void pestat(const bm2_opt *opt, const bm2_sam_opt *so, int64_t l_pac, int n_reads, const bm2_alnreg_t *alnregs, const int64_t *reg_off, PeStat pes[4]) {
+    const int64_t top = so->max_ins > 0 ? so->max_ins : 0;       // bins 1 .. max_ins
+    std::vector<uint32_t> hist;
+    pestat_count(opt, so, l_pac, n_reads >> 1, alnregs, reg_off, top, hist);
+    pestat_model(hist.data(), top, pes);
 }
 
 // bns_fetch_seq (bntseq.cpp:453-482) on the unpacked reference: [*beg, *end) clamped to the contig (strand-aware) that holds mid
@@ -1671,6 +1691,9 @@ bm2h_rescue_hook::bm2h_rescue_hook(bm2h_rescue_batch_fn fn, void *user) { t_resc
 bm2h_rescue_hook::~bm2h_rescue_hook() { t_rescue_fn = nullptr; t_rescue_user = nullptr; }
 bm2h_plan_hook::bm2h_plan_hook(bm2h_plan_batch_fn fn, bm2h_ksw_resident_fn qfn, void *user) { t_plan_fn = fn; t_planq_fn = qfn; t_plan_user = user; }
 bm2h_plan_hook::~bm2h_plan_hook() { t_plan_fn = nullptr; t_planq_fn = nullptr; t_plan_user = nullptr; }
+bm2h_pestat_hook::bm2h_pestat_hook(bm2h_pestat_batch_fn fn, void *user) { t_pestat_fn = fn; t_pestat_user = user; }
+bm2h_pestat_hook::~bm2h_pestat_hook() { t_pestat_fn = nullptr; t_pestat_user = nullptr; }
+uint64_t bm2h_tail_epoch() { return t_tail_epoch; }
 
 int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) {
     if (hit_off[0] < 0) { bm2_set_error("%s: hit_off[0] is negative", who); return BM2_EINVAL; }
@@ -1715,6 +1738,7 @@ extern "C" int bm2_pe_decide(const bm2_index_desc *idx, const bm2_opt *opt, cons
 namespace {
 std::atomic<long long> g_rs_pairs{0}, g_rs_tasks{0}, g_rs_added{0}, g_rs_redone{0};
 std::atomic<long long> g_pl_pairs{0}, g_pl_tasks{0}, g_pl_qbytes{0};
+std::atomic<long long> g_ps_pairs{0}, g_ps_counted{0}, g_ps_up{0}, g_ps_shared{0};
 void pes_of(const bm2_pestat in[4], PeStat pes[4]) {
     for (int d = 0; d < 4; ++d) { pes[d].low = in[d].low; pes[d].high = in[d].high; pes[d].failed = in[d].failed; pes[d].avg = in[d].avg; pes[d].std = in[d].std; }
 }
@@ -1734,6 +1758,36 @@ extern "C" void bm2_sam_rescue_plan_stats(int64_t *pairs, int64_t *tasks, int64_
     if (pairs) *pairs = g_pl_pairs.load();
     if (tasks) *tasks = g_pl_tasks.load();
     if (query_bytes) *query_bytes = g_pl_qbytes.load();
+}
+
+// ---- the insert-size model of a batch of pairs: the host form (the oracle of pestat.hip), the model half behind a name, the counters
+void bm2h_pestat_stats_set(long long pairs, long long counted, long long hit_bytes_up) { g_ps_pairs = pairs; g_ps_counted = counted; g_ps_up = hit_bytes_up; g_ps_shared = 0; }
+void bm2h_pestat_stats_shared(long long hit_bytes, bool add) { if (add) g_ps_shared += hit_bytes; else g_ps_shared = hit_bytes; }
+extern "C" void bm2_sam_pestat_stats(int64_t *pairs, int64_t *counted, int64_t *hit_bytes_up, int64_t *hit_bytes_shared) {
+    if (pairs) *pairs = g_ps_pairs.load();
+    if (counted) *counted = g_ps_counted.load();
+    if (hit_bytes_up) *hit_bytes_up = g_ps_up.load();
+    if (hit_bytes_shared) *hit_bytes_shared = g_ps_shared.load();
+}
+void bm2h_pestat_model(const uint32_t *hist, int64_t top, bm2_pestat out[4]) {
+    PeStat pes[4];
+    pestat_model(hist, top, pes);
+    for (int d = 0; d < 4; ++d) { out[d].low = pes[d].low; out[d].high = pes[d].high; out[d].failed = pes[d].failed; out[d].pad = 0; out[d].avg = pes[d].avg; out[d].std = pes[d].std; }
+}
+extern "C" int bm2_pe_stat(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                           const int64_t *hit_off, bm2_pestat pes[4], uint32_t *hist, int64_t hist_cap) {
+    if (!idx || !opt || !so || n_pairs < 0 || !hit_off || !pes || hist_cap < 0) { bm2_set_error("bm2_pe_stat: bad argument"); return BM2_EINVAL; }
+    int rc = bm2h_check_hit_off("bm2_pe_stat", n_pairs, hit_off);
+    if (rc) return rc;
+    if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("bm2_pe_stat: bad argument"); return BM2_EINVAL; }
+    if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_pe_stat: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
+    const int64_t top = so->max_ins > 0 ? so->max_ins : 0;
+    if (hist && hist_cap < 4 * (top + 1)) { bm2_set_error("bm2_pe_stat: the histogram takes %lld counts, room for %lld", (long long)(4 * (top + 1)), (long long)hist_cap); return BM2_ECAP; }
+    std::vector<uint32_t> h;
+    pestat_count(opt, so, idx->l_pac, n_pairs, hits, hit_off, top, h);
+    bm2h_pestat_model(h.data(), top, pes);
+    if (hist) memcpy(hist, h.data(), h.size() * sizeof(uint32_t));
+    return BM2_OK;
 }
 
 int bm2h_check_rescue_tasks(const char *who, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
@@ -2087,7 +2141,9 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         if (!t_plan_fn || !t_planq_fn || !fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PLAN needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
         if ((so->flag & F_NO_RESCUE) || so->rescue_inline) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PLAN plans the rescue batch: not with MEM_F_NO_RESCUE or rescue_inline"); return BM2_EINVAL; }
     }
+    if ((so->flag & BM2_SAM_F_DEVICE_PESTAT) && !t_pestat_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PESTAT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0, dev_plan = (so->flag & BM2_SAM_F_DEVICE_PLAN) != 0;
+    const bool dev_pestat = (so->flag & BM2_SAM_F_DEVICE_PESTAT) != 0 && !pes_in;       // (a model that is given leaves nothing to compute)
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
     if (so->max_ins > (1 << 24)) { bm2_set_error("bm2_sam_pe: max_ins above 2^24 is not supported (the insert sizes are counted in a histogram)"); return BM2_EUNSUP; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
@@ -2111,13 +2167,23 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     prof.mark("names");
     PeStat pes[4];
     if (pes_in) for (int d = 0; d < 4; ++d) { pes[d].low = pes_in[d].low; pes[d].high = pes_in[d].high; pes[d].failed = pes_in[d].failed; pes[d].avg = pes_in[d].avg; pes[d].std = pes_in[d].std; }
-    else pestat(opt, so, idx->l_pac, n, alnregs, reg_off, pes);  // per chunk, as mem_process_seqs does (bwamem.cpp:1366-1370)
+    else if (!dev_pestat) pestat(opt, so, idx->l_pac, n, alnregs, reg_off, pes);  // per chunk, as mem_process_seqs does (bwamem.cpp:1366-1370)
+    // BM2_SAM_F_DEVICE_PESTAT: the counting half on the device (the chunk's hits and offsets go up, four histograms come down), the model
+    // half by the same host code.  The call has a number until it returns: the plan hook may find this call's hits where they lie.
+    struct TailEpoch { TailEpoch(bool on) { t_tail_epoch = on ? ++g_tail_epoch : 0; } ~TailEpoch() { t_tail_epoch = 0; } } tail_epoch(dev_pestat);
+    if (so->flag & BM2_SAM_F_DEVICE_PESTAT) bm2h_pestat_stats_set(0, 0, 0);
+    if (dev_pestat) {
+        bm2_pestat pq[4];
+        const int rc = t_pestat_fn(t_pestat_user, opt, so, n >> 1, alnregs, reg_off, pq);
+        if (rc) return rc;
+        pes_of(pq, pes);
+    }
     if (pes_out) for (int d = 0; d < 4; ++d) { pes_out[d].low = pes[d].low; pes_out[d].high = pes[d].high; pes_out[d].failed = pes[d].failed; pes_out[d].pad = 0; pes_out[d].avg = pes[d].avg; pes_out[d].std = pes[d].std; }
     // Mate rescue in three steps, the shape a device kernel needs: plan every pair's alignments on the hit lists as they stand,
     // run them all as one batch (here: host threads over single tasks), then process the pairs with the results at hand.
     // so->rescue_inline = 1 aligns inside the pair loop as mem_sam_pe does; the output is the same.
     const int n_pairs = n >> 1;
-    prof.mark("pestat");
+    prof.mark(dev_pestat ? "pestat (device)" : "pestat");
     // (the flat arrays of the batch live in buffers the calling thread keeps from chunk to chunk: no fresh pages per chunk)
     static thread_local PeWork W_of_this_thread;
     PeWork &W = W_of_this_thread;                                // (a reference: the lambdas below run on the workers, whose own thread_local objects are other objects)
@@ -2508,6 +2574,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (so->flag & BM2_SAM_F_DEVICE_DECIDE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_DECIDE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_RESCUE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_RESCUE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_PLAN) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PLAN is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_PESTAT) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PESTAT is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);

@@ -458,6 +458,28 @@ int bm2_pe_rescue_queries_dev(bm2_ctx *c, const bm2_reads *reads, int64_t n_task
  * since: by that tail's rescue batch, or by a bm2_pe_rescue_queries call of either form (which reports no pairs). */
 void bm2_sam_rescue_plan_stats(int64_t *pairs, int64_t *tasks, int64_t *query_bytes);
 
+/* ---- the insert-size model of a batch of pairs (mem_pestat, bwamem_pair.cpp:81-148).  A pair whose ends both have hits, whose best
+ * hits are unique enough (cal_sub <= 0.8 * score on either end) and lie on one contig adds one to bin [dir][is] of four histograms when
+ * its insert size is in [1, max_ins]; quartiles, the trimmed mean and deviation, the bounds and the `failed` marks are read off the counts.
+ * bm2_pe_stat (host; the oracle) and bm2_pe_stat_dev (pestat.hip: the counting on the device, l_pac from the context -- BM2_EINVAL for
+ * one created without an index -- the model by the same host code) fill pes[4].  Lists and offsets as for bm2_pe_rescue_plan: hit_off has
+ * 2 * n_pairs + 1 entries and may start anywhere.  hist = NULL, or room for 4 * (max(max_ins, 0) + 1) counts, which receives the merged
+ * histogram laid out [dir][v]; BM2_ECAP when hist_cap is smaller.  max_ins > 2^24: BM2_EUNSUP.  n_pairs == 0 or max_ins <= 0: four failed
+ * models, every count zero. */
+int bm2_pe_stat(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                const int64_t *hit_off, bm2_pestat pes[4], uint32_t *hist, int64_t hist_cap);
+int bm2_pe_stat_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
+                    const int64_t *hit_off, bm2_pestat pes[4], uint32_t *hist, int64_t hist_cap);
+/* A library-private bit of bm2_sam_opt.flag, alone or with any of the four bits above, with or without mate rescue: bm2_sam_pe_dev and
+ * bm2_sam_pe_dev_multi called without a model (pes_in == NULL) take the chunk's model from bm2_pe_stat_dev's kernel on their context(s)
+ * (hits and offsets go up, four histograms come down).  With BM2_SAM_F_DEVICE_PLAN as well, the plan reads the hits where the model left
+ * them and uploads only the read lengths.  With pes_in given there is nothing to compute and the bit does nothing.  Same bytes.  Off by
+ * default.  bm2_sam_pe and the single-end entry points answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_PESTAT 0x10000000
+/* of the last bm2_pe_stat_dev call on this process, or of the last tail with the bit: its pairs, the pairs counted into a bin, the bytes
+ * of hits it uploaded, and how many bytes of hits the plan of the same tail call found resident and did not send again. */
+void bm2_sam_pestat_stats(int64_t *pairs, int64_t *counted, int64_t *hit_bytes_up, int64_t *hit_bytes_shared);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

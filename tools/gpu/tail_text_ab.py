@@ -13,6 +13,9 @@ the decide bit, with both others; the result then holds bm2_sam_rescue_apply_sta
 --bit plan|plan+rescue|plan+rescue+decide+text: BM2_SAM_F_DEVICE_PLAN (mate rescue planned by bm2_pe_rescue_plan_dev's kernels, the rescue
 batch's queries made on the device) alone, with the rescue bit, with all three others; the result then holds bm2_sam_rescue_plan_stats and
 the bytes the plan and the queries move.
+--bit pestat|pestat+plan: BM2_SAM_F_DEVICE_PESTAT (the chunk's insert-size model counted by bm2_pe_stat_dev's kernel) alone and with the
+plan bit, which then reads the hits where the model left them; the result holds bm2_sam_pestat_stats and the bytes the model moves.  The
+phases to read: `sam_pe: pestat` against `sam_pe: pestat (device)`, and `pe_plan_dev: H2D` of --bit plan against --bit pestat+plan.
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -104,7 +107,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan"))
     a = ap.parse_args()
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
@@ -131,7 +134,7 @@ def main():
     variants = a.variants.split(",")
     on = set({"both": "text+decide", "all": "text+decide+rescue"}.get(a.bit, a.bit).split("+"))
     bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if "text" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if "decide" in on else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0)
+           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PESTAT", 0) if "pestat" in on else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
@@ -142,7 +145,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided, rescued, planned_dev = None, None, None, None, None
+    counters, first, decided, rescued, planned_dev, model_dev = None, None, None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -160,6 +163,8 @@ def main():
                 rescued = bm2.sam_rescue_apply_stats() + bm2.sam_rescue_stats()
             if v == "on" and "plan" in on:
                 planned_dev = bm2.sam_rescue_plan_stats() + bm2.sam_rescue_stats()
+            if v == "on" and "pestat" in on:
+                model_dev = bm2.sam_pestat_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -193,6 +198,10 @@ def main():
         mine["plan_stats"] = {"pairs": pairs, "tasks": tasks, "query_bytes": q_bytes, "planned": planned, "used": used, "missed": missed}
         mine["plan_pcie"] = {"plan_up": 96 * n_hits + 8 * (2 * pairs + 1) + 4 * 2 * pairs, "plan_down": 64 * tasks + 8 * (pairs + 1),
                              "queries_up_at_most": int(ch.f.n_bases) + 24 * tasks, "queries_up_without_the_bit": q_bytes}
+    if model_dev is not None:                                    # (pestat.hip: 96 B a hit and 8 B a list offset up, 16 B a bin of one orientation down)
+        pairs, counted, up, shared = model_dev
+        mine["pestat_stats"] = {"pairs": pairs, "counted": counted, "hit_bytes_up": up, "hit_bytes_shared": shared}
+        mine["pestat_pcie"] = {"up": up + 8 * (2 * pairs + 1), "down": 16 * (so["on"].max_ins + 1), "plan_up_saved": shared + (8 * (2 * pairs + 1) if shared else 0)}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

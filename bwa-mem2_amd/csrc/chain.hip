@@ -11,6 +11,7 @@
 #include "pipeline.h"
 #include "chain_dev.h"
 #include "ksort_dev.h"
+#include <type_traits>
 
 #define BM2_CHAIN_TIERS 8          // stream / event slots kept for the tier launches (five tiers are launched)
 #define CHAIN_CUR_SLOTS 5           // work cursors item_cur[0..4]: the first five tiers; [5], [6]: the overflow / island launch; further tiers: item_cur[CHAIN_CUR_EXTRA ..]
@@ -357,18 +358,128 @@ template <bool SP = false> static __device__ int bt_traverse(const BTree &b, int
     return n;
 }
 
+// ---- the same tree over COMPACT nodes (chain_dev.h: CNode, 40 bytes instead of 160), the form k_chain_heavy keeps in LDS: a node holds no copy of its
+// keys' sort fields -- the chains lie in the same LDS, so a probe reads ch[key].pos there (a chain's pos never changes once it is in the tree).  Statement
+// for statement the memory form of bt_put / bt_lower / bt_split / bt_traverse above; only where a key's sort field is read from differs, so the split
+// points, the placement of equal keys, the in-order sequence and every lower bound are the same (tests/test_btree_compact.py drives the two side by side).
+struct CTree { CNode *nodes; int n_nodes, root, n_keys; const CChain *ch; };
+static __device__ __forceinline__ int bt_new(CTree &b, int internal) {
+    CNode &z = b.nodes[b.n_nodes];
+    z.n = 0; z.is_internal = (uint8_t)internal;
+    return b.n_nodes++;
+}
+static __device__ __forceinline__ int bt_getp_aux(const CTree &b, const CNode &x, int64_t k, int &r) {
+    int begin = 0, end = x.n;
+    if (x.n == 0) return -1;
+    while (begin < end) {
+        const int mid = (begin + end) >> 1;
+        if (b.ch[x.key[mid]].pos < k) begin = mid + 1; else end = mid;
+    }
+    if (begin == x.n) { r = 1; return x.n - 1; }
+    const int64_t kp = b.ch[x.key[begin]].pos;
+    r = (kp < k) - (k < kp);
+    if (r < 0) --begin;
+    return begin;
+}
+static __device__ int bt_lower(const CTree &b, int64_t k) {
+    int lower = -1, x = b.root, r = 0;
+    while (x >= 0) {
+        const CNode &nd = b.nodes[x];
+        const int i = bt_getp_aux(b, nd, k, r);
+        if (i >= 0 && r == 0) return nd.key[i];
+        if (i >= 0) lower = nd.key[i];
+        if (!nd.is_internal) return lower;
+        x = nd.ptr[i + 1];
+    }
+    return lower;
+}
+static __device__ void bt_split(CTree &b, int xi, int i, int yi) {
+    const int zi = bt_new(b, b.nodes[yi].is_internal);
+    CNode &x = b.nodes[xi], &y = b.nodes[yi], &z = b.nodes[zi];
+    z.n = BT_T - 1;
+    for (int t = 0; t < BT_T - 1; t++) z.key[t] = y.key[BT_T + t];
+    if (y.is_internal) for (int t = 0; t < BT_T; t++) z.ptr[t] = y.ptr[BT_T + t];
+    y.n = BT_T - 1;
+    for (int t = x.n; t > i; t--) x.ptr[t + 1] = x.ptr[t];
+    x.ptr[i + 1] = (int16_t)zi;
+    for (int t = x.n - 1; t >= i; t--) x.key[t + 1] = x.key[t];
+    x.key[i] = y.key[BT_T - 1];
+    ++x.n;
+}
+static __device__ void bt_put(CTree &b, int key, int64_t k) {      // (ch[key] is written before its key goes in: the caller has just made the chain)
+    ++b.n_keys;
+    if (b.nodes[b.root].n == 2 * BT_T - 1) {
+        const int s = bt_new(b, 1), r = b.root;
+        b.root = s; b.nodes[s].ptr[0] = (int16_t)r;
+        bt_split(b, s, 0, r);
+    }
+    int xi = b.root, r;
+    for (;;) {
+        CNode &x = b.nodes[xi];
+        if (!x.is_internal) {
+            const int i = bt_getp_aux(b, x, k, r);
+            for (int t = x.n - 1; t > i; t--) x.key[t + 1] = x.key[t];
+            x.key[i + 1] = (int16_t)key;
+            ++x.n;
+            return;
+        }
+        int i = bt_getp_aux(b, x, k, r) + 1;
+        if (b.nodes[x.ptr[i]].n == 2 * BT_T - 1) {
+            bt_split(b, xi, i, x.ptr[i]);
+            if (k > b.ch[x.key[i]].pos) ++i;
+        }
+        xi = x.ptr[i];
+    }
+}
+static __device__ int bt_traverse(const CTree &b, int16_t *out) {
+    int n = 0, sp = 0;
+    int stk_node[24], stk_i[24];
+    stk_node[0] = b.root; stk_i[0] = 0;
+    while (sp >= 0) {
+        const CNode &nd = b.nodes[stk_node[sp]];
+        const int i = stk_i[sp];
+        if (nd.is_internal) {
+            if (i <= nd.n) {
+                if (i > 0) out[n++] = nd.key[i - 1];             // key i-1 is emitted when we come back from child i-1
+                stk_i[sp] = i + 1;
+                ++sp; stk_node[sp] = nd.ptr[i]; stk_i[sp] = 0;
+            } else --sp;
+        } else {
+            for (int t = 0; t < nd.n; t++) out[n++] = nd.key[t];
+            --sp;
+        }
+    }
+    return n;
+}
+
 // ---------------------------------------------------------------- chaining of one read
+// The code below is written once over both forms of the working records (chain_dev.h): CH = WChain or CChain (same field names), OT = the type of an
+// entry of the order arrays, SD = where the seeds are -- WSeed records, or the staged arrays plus a successor each (CSeeds) -- read through these:
+static __device__ __forceinline__ int64_t sd_rbeg(const WSeed *sd, int i) { return sd[i].rbeg; }
+static __device__ __forceinline__ int sd_qbeg(const WSeed *sd, int i) { return sd[i].qbeg; }
+static __device__ __forceinline__ int sd_len(const WSeed *sd, int i) { return sd[i].len; }
+static __device__ __forceinline__ int sd_next(const WSeed *sd, int i) { return sd[i].next; }
+static __device__ __forceinline__ void sd_link(WSeed *sd, int i, int nx) { sd[i].next = nx; }
+static __device__ __forceinline__ void sd_put(WSeed *sd, int i, const WSeed &p) { sd[i] = p; sd[i].next = -1; }      // seed p becomes seed i, the last of its chain
+static __device__ __forceinline__ int64_t sd_rbeg(const CSeeds &sd, int i) { return sd.rbeg[i]; }
+static __device__ __forceinline__ int sd_qbeg(const CSeeds &sd, int i) { return (int)(sd.ql[i] & 0x7fffu); }
+static __device__ __forceinline__ int sd_len(const CSeeds &sd, int i) { return (int)((sd.ql[i] >> 15) & 0xffffu); }
+static __device__ __forceinline__ int sd_next(const CSeeds &sd, int i) { return sd.next[i]; }
+static __device__ __forceinline__ void sd_link(const CSeeds &sd, int i, int nx) { sd.next[i] = (int16_t)nx; }
+static __device__ __forceinline__ void sd_put(const CSeeds &sd, int i, const WSeed &) { sd.next[i] = -1; }             // (i is the seed's staged index: its fields are there already)
+
 // test_and_merge, bwamem.cpp:357-399
-static __device__ int test_and_merge(const ChainParams &o, int64_t l_pac, WChain &c, const WSeed &p, int seed_rid,
-                                     WSeed *seeds, int si) {
+template <class CH, class SD>
+static __device__ int test_and_merge(const ChainParams &o, int64_t l_pac, CH &c, const WSeed &p, int seed_rid,
+                                     SD seeds, int si) {
     const int64_t qend = c.last_qbeg + c.last_len, rend = c.last_rbeg + c.last_len;
     if (seed_rid != c.rid) return 0;
     if (p.qbeg >= c.first_qbeg && p.qbeg + p.len <= qend && p.rbeg >= c.pos && p.rbeg + p.len <= rend) return 1;
     if ((c.last_rbeg < l_pac || c.pos < l_pac) && p.rbeg >= l_pac) return 0;
     const int64_t x = p.qbeg - c.last_qbeg, y = p.rbeg - c.last_rbeg;
     if (y >= 0 && x - y <= o.w && y - x <= o.w && x - c.last_len < o.max_chain_gap && y - c.last_len < o.max_chain_gap) {
-        seeds[si] = p; seeds[si].next = -1;
-        seeds[c.tail].next = si;
+        sd_put(seeds, si, p);
+        sd_link(seeds, c.tail, si);
         c.tail = si; c.n++;
         c.last_rbeg = p.rbeg; c.last_qbeg = p.qbeg; c.last_len = p.len;
         return 2;      // merged and consumed the seed slot
@@ -377,20 +488,21 @@ static __device__ int test_and_merge(const ChainParams &o, int64_t l_pac, WChain
 }
 
 // mem_chain_weight, bwamem.cpp:429-448
-static __device__ int chain_weight(const WChain &c, const WSeed *seeds) {
+template <class CH, class SD>
+static __device__ int chain_weight(const CH &c, SD seeds) {
     int64_t end = 0; int w = 0, tmp;
-    for (int si = c.head; si >= 0; si = seeds[si].next) {
-        const WSeed &s = seeds[si];
-        if (s.qbeg >= end) w += s.len;
-        else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-        end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
+    for (int si = c.head; si >= 0; si = sd_next(seeds, si)) {
+        const int s_qbeg = sd_qbeg(seeds, si), s_len = sd_len(seeds, si);
+        if (s_qbeg >= end) w += s_len;
+        else if (s_qbeg + s_len > end) w += (int)(s_qbeg + s_len - end);
+        end = end > s_qbeg + s_len ? end : s_qbeg + s_len;
     }
     tmp = w; w = 0; end = 0;
-    for (int si = c.head; si >= 0; si = seeds[si].next) {
-        const WSeed &s = seeds[si];
-        if (s.rbeg >= end) w += s.len;
-        else if (s.rbeg + s.len > end) w += (int)(s.rbeg + s.len - end);
-        end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
+    for (int si = c.head; si >= 0; si = sd_next(seeds, si)) {
+        const int64_t s_rbeg = sd_rbeg(seeds, si); const int s_len = sd_len(seeds, si);
+        if (s_rbeg >= end) w += s_len;
+        else if (s_rbeg + s_len > end) w += (int)(s_rbeg + s_len - end);
+        end = end > s_rbeg + s_len ? end : s_rbeg + s_len;
     }
     w = w < tmp ? w : tmp;
     return w < 1 << 30 ? w : (1 << 30) - 1;
@@ -419,8 +531,11 @@ static __device__ __forceinline__ void chain_finish_one(const DevIndex &ix, cons
         if (os[s0].rbeg < ix.l_pac) rmax1 = ix.l_pac; else rmax0 = ix.l_pac;
     }
     {
-        int is_rev;
-        const int rid = pos2rid(ix, depos(ix, os[s0].rbeg, is_rev));
+        // bns_fetch_seq_v2's contig is bns_pos2rid(bns_depos(first seed)): the chain's own rid -- bns_intv2rid returned exactly that for the seed that founded
+        // the chain (rid_b of a non-negative result), test_and_merge admits only seeds of the same rid, and the seed filter leaves the first seed's contig
+        // unchanged (every seed of the chain has it) -- so the binary search over the contig table is not repeated per kept chain
+        const int is_rev = os[s0].rbeg >= ix.l_pac;
+        const int rid = d.rid;
         int64_t far_beg = ix.ann_offset[rid], far_end = far_beg + ix.ann_len[rid];
         if (is_rev) { const int64_t tmp = far_beg; far_beg = (ix.l_pac << 1) - far_end; far_end = (ix.l_pac << 1) - tmp; }
         rmax0 = rmax0 > far_beg ? rmax0 : far_beg;
@@ -445,7 +560,8 @@ static __device__ __forceinline__ void chain_finish_one(const DevIndex &ix, cons
 // The rest of mem_chain_flt (bwamem.cpp:548-624) and the hand-over to the extension stage, for the n chains ord[0..n) -- the chains that
 // passed the weight test, in key order -- of read r: introsort by weight, overlap filter, kept chains with their seeds made contiguous.
 // kept_list: scratch for n ints (the B-tree's nodes are no longer needed when this runs).
-static __device__ void chain_finish_read(const ChainParams &o, int r, WChain *ch, WSeed *sd, int32_t *ord, int32_t *kept_list, int n, int64_t base,
+template <class CH, class SD, class OT>
+static __device__ void chain_finish_read(const ChainParams &o, int r, CH *ch, SD sd, OT *ord, OT *kept_list, int n, int64_t base,
                                          float frac_rep, DevChain *chn, DevSeed *seeds_out, int32_t *seed_owner, int32_t *n_chain_out, int32_t *n_reg_out,
                                          const DevIndex *fix = nullptr, const FinishOut *fo = nullptr /* both set: this lane does k_chain_finish's part too */) {
     int k;
@@ -455,12 +571,12 @@ static __device__ void chain_finish_read(const ChainParams &o, int r, WChain *ch
         ch[ord[0]].kept = 3;
         kept_list[n_kept++] = 0;
         for (int i = 1; i < n; ++i) {
-            WChain &ci = ch[ord[i]];
+            CH &ci = ch[ord[i]];
             const int beg_i = ci.first_qbeg, end_i = ci.last_qbeg + ci.last_len;
             int large_ovlp = 0, kk;
             for (kk = 0; kk < n_kept; ++kk) {
                 const int j = kept_list[kk];
-                WChain &cj = ch[ord[j]];
+                CH &cj = ch[ord[j]];
                 const int beg_j = cj.first_qbeg, end_j = cj.last_qbeg + cj.last_len;
                 const int b_max = beg_j > beg_i ? beg_j : beg_i;
                 const int e_min = end_j < end_i ? end_j : end_i;
@@ -477,7 +593,7 @@ static __device__ void chain_finish_read(const ChainParams &o, int r, WChain *ch
             if (kk == n_kept) { kept_list[n_kept++] = i; ci.kept = large_ovlp ? 2 : 3; }
         }
         for (int i = 0; i < n_kept; ++i) {
-            const WChain &c = ch[ord[kept_list[i]]];
+            const CH &c = ch[ord[kept_list[i]]];
             if (c.first >= 0) ch[ord[c.first]].kept = 1;
         }
         int i2;
@@ -495,13 +611,13 @@ static __device__ void chain_finish_read(const ChainParams &o, int r, WChain *ch
     DevSeed *os = seeds_out + base;
     int n_seed = 0, n_reg = 0;
     for (int i = 0; i < n; i++) {
-        const WChain &c = ch[ord[i]];
+        const CH &c = ch[ord[i]];
         DevChain d;
         d.pos = c.pos; d.seed_off = base + n_seed; d.n = c.n; d.rid = c.rid; d.w = c.w; d.kept = c.kept; d.first = c.first;
         d.is_alt = c.is_alt; d.read = r; d.frac_rep = frac_rep; d.rmax0 = 0; d.rmax1 = 0;
         const int s0 = n_seed;
-        for (int si = c.head; si >= 0; si = sd[si].next) {
-            DevSeed s; s.rbeg = sd[si].rbeg; s.qbeg = sd[si].qbeg; s.len = sd[si].len; s.score = sd[si].len; s.aln = -1;
+        for (int si = c.head; si >= 0; si = sd_next(sd, si)) {
+            DevSeed s; s.rbeg = sd_rbeg(sd, si); s.qbeg = sd_qbeg(sd, si); s.len = sd_len(sd, si); s.score = s.len; s.aln = -1;
             os[n_seed++] = s;
         }
         d.reg0 = 0; d.pad = 0;
@@ -516,11 +632,13 @@ static __device__ void chain_finish_read(const ChainParams &o, int r, WChain *ch
 // ---- mem_chain_flt again, for a WHOLE WAVEFRONT (BM2_CHAIN_COOP_FLT; chain_finish_read above is what one lane runs and stays as it is): the walk over
 // the kept chains is quadratic in the chains of a repeat-rich read -- 64 kept chains at a time, one per lane (flt_kept_coop); the weight sort before it
 // and the rest + the read's output after it (flt_rest_emit: the same statements as in chain_finish_read) are lane 0's.
-static __device__ __forceinline__ void flt_sort(const WChain *ch, int32_t *ord, int n) {
+template <class CH, class OT>
+static __device__ __forceinline__ void flt_sort(const CH *ch, OT *ord, int n) {
     k_introsort_flat(n, ord, [&](int32_t x, int32_t y) { return ch[x].w > ch[y].w; });     // flt_lt, bwamem.cpp:61
 }
 // the overlap test of chain i (span [beg_i, end_i), weight w_i) against the kept chain cj: bit 0 = large overlap, bit 1 = ... and i is dropped (bwamem.cpp:570-584)
-static __device__ __forceinline__ int flt_ovlp(const ChainParams &o, const WChain &cj, int beg_i, int end_i, int w_i, int alt_i) {
+template <class CH>
+static __device__ __forceinline__ int flt_ovlp(const ChainParams &o, const CH &cj, int beg_i, int end_i, int w_i, int alt_i) {
     const int beg_j = cj.first_qbeg, end_j = cj.last_qbeg + cj.last_len;
     const int b_max = beg_j > beg_i ? beg_j : beg_i;
     const int e_min = end_j < end_i ? end_j : end_i;
@@ -540,7 +658,8 @@ static __device__ __forceinline__ void flt_sync() {              // lanes of ONE
 // The same walk by the 64 lanes of a (converged) wavefront: chain i meets 64 kept chains at a time, one per lane.  The serial walk stops at
 // the FIRST kept chain that drops i, and every kept chain up to and including that one which overlaps i largely gets `first` (if it has none):
 // a ballot of the drop test gives the stopping lane, the lanes up to it apply their own chain's side effect -- no two lanes touch one chain.
-static __device__ int flt_kept_coop(const ChainParams &o, WChain *ch, const int32_t *ord, int32_t *kept_list, int n, int lane) {
+template <class CH, class OT>
+static __device__ int flt_kept_coop(const ChainParams &o, CH *ch, const OT *ord, OT *kept_list, int n, int lane) {
     if (lane == 0) { ch[ord[0]].kept = 3; kept_list[0] = 0; }
     int n_kept = 1;
     flt_sync();
@@ -572,12 +691,13 @@ static __device__ int flt_kept_coop(const ChainParams &o, WChain *ch, const int3
     return n_kept;
 }
 // the rest of mem_chain_flt and the read's chains with contiguous seeds
-static __device__ void flt_rest_emit(const ChainParams &o, int r, WChain *ch, WSeed *sd, int32_t *ord, const int32_t *kept_list, int n, int n_kept, int64_t base,
+template <class CH, class SD, class OT>
+static __device__ void flt_rest_emit(const ChainParams &o, int r, CH *ch, SD sd, OT *ord, const OT *kept_list, int n, int n_kept, int64_t base,
                                      float frac_rep, DevChain *chn, DevSeed *seeds_out, int32_t *seed_owner, int32_t *n_chain_out, int32_t *n_reg_out) {
     int k;
     if (n > 0) {
         for (int i = 0; i < n_kept; ++i) {
-            const WChain &c = ch[ord[kept_list[i]]];
+            const CH &c = ch[ord[kept_list[i]]];
             if (c.first >= 0) ch[ord[c.first]].kept = 1;
         }
         int i2;
@@ -595,13 +715,13 @@ static __device__ void flt_rest_emit(const ChainParams &o, int r, WChain *ch, WS
     DevSeed *os = seeds_out + base;
     int n_seed = 0;
     for (int i = 0; i < n; i++) {
-        const WChain &c = ch[ord[i]];
+        const CH &c = ch[ord[i]];
         DevChain d;
         d.pos = c.pos; d.seed_off = base + n_seed; d.n = c.n; d.rid = c.rid; d.w = c.w; d.kept = c.kept; d.first = c.first;
         d.is_alt = c.is_alt; d.read = r; d.frac_rep = frac_rep; d.rmax0 = 0; d.rmax1 = 0;
         const int s0 = n_seed;
-        for (int si = c.head; si >= 0; si = sd[si].next) {
-            DevSeed s; s.rbeg = sd[si].rbeg; s.qbeg = sd[si].qbeg; s.len = sd[si].len; s.score = sd[si].len; s.aln = -1;
+        for (int si = c.head; si >= 0; si = sd_next(sd, si)) {
+            DevSeed s; s.rbeg = sd_rbeg(sd, si); s.qbeg = sd_qbeg(sd, si); s.len = sd_len(sd, si); s.score = s.len; s.aln = -1;
             os[n_seed++] = s;
         }
         d.reg0 = 0; d.pad = 0;
@@ -612,17 +732,23 @@ static __device__ void flt_rest_emit(const ChainParams &o, int r, WChain *ch, WS
     n_reg_out[r] = 0;              // set by k_chain_finish
 }
 // A read whose finish the caller runs itself (with all its lanes: chain_finish_coop): what chain_one_read would have passed to chain_finish_read
-struct DeferFinish { int valid, r, n; int64_t base; float frac_rep; WChain *ch; WSeed *sd; int32_t *ord; int32_t *kept; };
+// (compact: the read was chained in the compact form -- ch is a CChain *, ord / kept are int16_t *, sd is the seeds' `next` array: k_chain_heavy puts the types back)
+struct DeferFinish { int valid, r, n; int64_t base; float frac_rep; WChain *ch; WSeed *sd; int32_t *ord; int32_t *kept; int compact; };
+template <class CH, class SD, class OT>
+static __device__ void chain_finish_coop_on(const ChainParams &o, int r, int n, int64_t base, float frac_rep, CH *ch, SD sd, OT *ord, OT *kept, int lane, DevChain *chn,
+                                            DevSeed *seeds_out, int32_t *seed_owner, int32_t *n_chain_out, int32_t *n_reg_out) {
+    int n_kept = 0;
+    if (n > 0) {
+        if (lane == 0) flt_sort(ch, ord, n);
+        flt_sync();
+        n_kept = flt_kept_coop(o, ch, ord, kept, n, lane);
+    }
+    if (lane == 0) flt_rest_emit(o, r, ch, sd, ord, kept, n, n_kept, base, frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out);
+    flt_sync();
+}
 static __device__ void chain_finish_coop(const ChainParams &o, const DeferFinish &d, int lane, DevChain *chn, DevSeed *seeds_out, int32_t *seed_owner,
                                          int32_t *n_chain_out, int32_t *n_reg_out) {      // (every lane of the wavefront, converged; `d` is the same in all of them)
-    int n_kept = 0;
-    if (d.n > 0) {
-        if (lane == 0) flt_sort(d.ch, d.ord, d.n);
-        flt_sync();
-        n_kept = flt_kept_coop(o, d.ch, d.ord, d.kept, d.n, lane);
-    }
-    if (lane == 0) flt_rest_emit(o, d.r, d.ch, d.sd, d.ord, d.kept, d.n, n_kept, d.base, d.frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out);
-    flt_sync();
+    chain_finish_coop_on(o, d.r, d.n, d.base, d.frac_rep, d.ch, d.sd, d.ord, d.kept, lane, chn, seeds_out, seed_owner, n_chain_out, n_reg_out);
 }
 
 struct IslSeed { int64_t rbeg; uint32_t ql; int32_t rid; };           // a seed staged in global memory (k_chain_islands): ql = qbeg | len << 15 | is_alt << 31
@@ -632,6 +758,8 @@ struct IslHash { unsigned long long key; int32_t cnt, start; };        // key = 
 // them in the read's slices of global arrays; the wave-per-read kernel of seed-rich reads keeps them in LDS (k_chain_heavy).
 struct ChainWork {
     WChain *ch; WSeed *sd; BtNode *nodes; int32_t *ord;
+    // the compact form (chain_dev.h), for a read whose inputs are staged: 40-byte chains and nodes, a 16-bit successor per staged seed, 16-bit order entries
+    CChain *cch; CNode *cnodes; int16_t *nx; int16_t *ord16;
     // inputs of the read staged by the whole wavefront before lane 0 walks them (k_chain_heavy, `staged`): per seed the reference
     // position, (qbeg | len << 15 | is_alt << 31) and the contig id bns_intv2rid gives; per SMEM (m | (n + 1) << 15 | repetitive << 31)
     int64_t *st_rbeg; uint32_t *st_ql; int32_t *st_rid; uint32_t *st_sm; bool staged;
@@ -640,8 +768,9 @@ struct ChainWork {
 };
 
 // mem_chain_seeds + mem_chain_flt for read r.  LIGHT: the lane-per-read kernel (global slices); otherwise the caller offers LDS
-// for up to lds_cap seeds in `lw`.
-template <bool LIGHT>
+// for up to lds_cap seeds in `lw`.  CPT (k_chain_heavy with staging): that LDS holds the compact form of the records, for a read the wavefront has staged;
+// any other read of such a launch (the last tier's beyond its cap) is chained on its global slices in the records they have always had.
+template <bool LIGHT, bool CPT = false>
 static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, int r, int n_reads, const int32_t *__restrict__ len,
                                       const bm2_smem_t *__restrict__ smems, const int32_t *__restrict__ smem_cnt,
                                       const int64_t *__restrict__ smem_off, const int64_t *__restrict__ sa_off,
@@ -667,15 +796,7 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
     const int64_t base = sa_off[so];
     const int n_sa = (int)(sa_off[so + n_sm] - base);
     if (n_sa == 0) return;
-    const bool in_lds = !LIGHT && n_sa <= lds_cap;
-    WChain *ch = in_lds ? lw->ch : wchain + base;
-    WSeed *sd = in_lds ? lw->sd : wseed + base;
-    int32_t *ord = in_lds ? lw->ord : order + base;
-    BtNode *nodes = in_lds ? lw->nodes : nodes_g + base;
-    BTree bt; bt.nodes = nodes; bt.n_nodes = 0; bt.n_keys = 0; bt.ch = ch;     // <= n_sa/4 + 1 nodes are ever needed
-    bt.reg = !in_lds && o.reg_nodes;
-    bt.root = bt_new(bt, 0);
-    int n_ch = 0, n_sd = 0;
+    const bool in_lds = !LIGHT && (CPT ? lw->staged : n_sa <= lds_cap);
     RidCache ridc; ridc.lo = 1; ridc.hi = 0; ridc.rid = -1;
     int b = 0, e = 0, l_rep = 0;
     const bool staged = !LIGHT && in_lds && lw->staged;
@@ -688,6 +809,13 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
         else e = e > se ? e : se;
     }
     l_rep += e - b;
+    // the walk and what follows it, over either form of the working records: ch, ord, kept (scratch of mem_chain_flt: the tree's nodes, no longer needed
+    // then) are pointers, sd is where the seeds are kept (WSeed * or CSeeds), bt the tree over `ch`
+    auto walk = [&](auto *ch, auto sd, auto &bt, auto *ord, auto *kept) {
+    using CH = typename std::remove_pointer<decltype(ch)>::type;
+    constexpr bool COMPACT = std::is_same<CH, CChain>::value;      // a seed's slot is then its staged index t, not its arrival number
+    bt.root = bt_new(bt, 0);
+    int n_ch = 0, n_sd = 0;
     // one flat loop over the read's seeds (SMEM-major, occurrence-minor -- the order of bwamem.cpp:879-905): the lanes of
     // a wavefront then run max(seeds per read) iterations instead of the sum over SMEM ranks of the per-rank maxima
     {
@@ -721,17 +849,17 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
                 const int lower = bt_lower(bt, s.rbeg);
                 if (lower < 0) to_add = 1;
                 else {
-                    const int m = test_and_merge(o, ix.l_pac, ch[lower], s, rid, sd, n_sd);
+                    const int m = test_and_merge(o, ix.l_pac, ch[lower], s, rid, sd, COMPACT ? t : n_sd);
                     if (m == 2) n_sd++;
                     else if (m == 0) to_add = 1;
                 }
             } else to_add = 1;
             if (to_add) {                                // bwamem.cpp:930-951
-                WChain c2;
+                CH c2;
                 c2.pos = s.rbeg; c2.last_rbeg = s.rbeg; c2.first_qbeg = s.qbeg; c2.last_qbeg = s.qbeg; c2.last_len = s.len;
-                c2.n = 1; c2.rid = rid; c2.is_alt = (staged || ist) ? alt_staged : (ix.ann_is_alt[rid] ? 1 : 0); c2.head = c2.tail = n_sd;
+                c2.n = 1; c2.rid = rid; c2.is_alt = (staged || ist) ? alt_staged : (ix.ann_is_alt[rid] ? 1 : 0); c2.head = c2.tail = COMPACT ? t : n_sd;
                 c2.w = 0; c2.kept = 0; c2.first = -1;
-                sd[n_sd] = s; n_sd++;
+                sd_put(sd, COMPACT ? t : n_sd, s); n_sd++;
                 ch[n_ch] = c2;
                 bt_put(bt, n_ch, c2.pos);
                 n_ch++;
@@ -746,19 +874,40 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
     // ---- mem_chain_flt, bwamem.cpp:506-624
     int k = 0;
     for (int i = 0; i < n; i++) {
-        WChain &c = ch[ord[i]];
+        CH &c = ch[ord[i]];
         c.first = -1; c.kept = 0;
         c.w = chain_weight(c, sd);
         if (c.w >= o.min_chain_weight) ord[k++] = ord[i];
     }
     if (k == 0 && n > 0) k = 1;      // quirk: an empty survivor list still processes the untouched a_[0] (bwamem.cpp:529-546)
     if (!LIGHT && defer) {
-        defer->r = r; defer->n = k; defer->base = base; defer->frac_rep = frac_rep; defer->ch = ch; defer->sd = sd; defer->ord = ord; defer->kept = (int32_t *)nodes;
+        defer->r = r; defer->n = k; defer->base = base; defer->frac_rep = frac_rep; defer->ord = (int32_t *)ord; defer->kept = (int32_t *)kept;
+        defer->ch = (WChain *)ch; defer->compact = COMPACT ? 1 : 0;
+        if constexpr (COMPACT) defer->sd = (WSeed *)sd.next; else defer->sd = sd;
         defer->valid = 1;
         return;
     }
-    chain_finish_read(o, r, ch, sd, ord, (int32_t *)nodes, k, base, frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, &ix, LIGHT ? fo : nullptr);
+    chain_finish_read(o, r, ch, sd, ord, kept, k, base, frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, &ix, LIGHT ? fo : nullptr);
     if (!LIGHT && lw && lw->clk) atomicAdd(lw->clk + 2, (unsigned long long)(wall_clock64() - t_walk));
+    };
+    if constexpr (CPT) {
+        if (in_lds) {
+            CTree bt; bt.nodes = lw->cnodes; bt.n_nodes = 0; bt.n_keys = 0; bt.ch = lw->cch;      // <= n_sa/4 + 1 nodes are ever needed
+            const CSeeds sd = { lw->st_rbeg, lw->st_ql, lw->nx };
+            walk(lw->cch, sd, bt, lw->ord16, (int16_t *)lw->cnodes);
+            return;
+        }
+    }
+    const bool lds_old = !CPT && in_lds;
+    WChain *ch = lds_old ? lw->ch : wchain + base;
+    WSeed *sd = lds_old ? lw->sd : wseed + base;
+    int32_t *ord = lds_old ? lw->ord : order + base;
+    BtNode *nodes = lds_old ? lw->nodes : nodes_g + base;
+    BTree bt; bt.nodes = nodes; bt.n_nodes = 0; bt.n_keys = 0; bt.ch = ch;     // <= n_sa/4 + 1 nodes are ever needed
+    // (a compact launch probes the nodes of the few reads it has to chain on their global slices IN MEMORY: with the register form inlined beside the compact
+    //  walk the kernel spilled 64 registers at three wavefronts per SIMD; the records and the tree are the same either way)
+    bt.reg = !CPT && !in_lds && o.reg_nodes;
+    walk(ch, sd, bt, ord, (int32_t *)nodes);
 }
 
 __global__ void __launch_bounds__(128, 6)
@@ -792,7 +941,9 @@ static __device__ __forceinline__ void chain_wave_sync() {      // lanes of one 
 // WPE: wavefronts per SIMD the register allocation leaves room for (BM2_CHAIN_HEAVY_WPE).  Left alone the cooperative instantiation takes 171 registers --
 // 176 allocated, TWO wavefronts per SIMD, eight per CU, where the tiers of the seed-poorest heavy reads could hold sixteen by their LDS; 3: 139 registers,
 // nothing spilled; 4: 128 registers and 32-64 more bytes of scratch
-template <bool COOP, int WPE>
+// CPT (BM2_CHAIN_LDS_COMPACT, needs staging): the LDS holds the COMPACT form of a staged read's records (chain_dev.h) -- 74 bytes per seed instead of 156:
+// chains 40, nodes 10, a 16-bit successor per seed 2, order 2 (the SMEM cuts of the staging live there before the walk needs it), staged inputs 20.
+template <bool COOP, int WPE, bool CPT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict__ len, const bm2_smem_t *__restrict__ smems,
               const int32_t *__restrict__ smem_cnt, const int64_t *__restrict__ smem_off, const int64_t *__restrict__ sa_off,
@@ -805,8 +956,22 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
     const int lane = threadIdx.x;
     ChainWork lw;
     lw.clk = clk;
-    int32_t *st_cut = nullptr;
-    {
+    typedef typename std::conditional<CPT, uint16_t, int32_t>::type CutT;      // (a cut is a seed count of the read: at most cap)
+    CutT *st_cut = nullptr;
+    if constexpr (CPT) {
+        size_t at = 0;                                                // (widest first: every array starts at a multiple of its element size)
+        lw.cch = (CChain *)(chain_lds + at); at += (size_t)cap * sizeof(CChain);
+        lw.st_rbeg = (int64_t *)(chain_lds + at); at += (size_t)cap * 8;
+        lw.st_ql = (uint32_t *)(chain_lds + at); at += (size_t)cap * 4;
+        lw.st_rid = (int32_t *)(chain_lds + at); at += (size_t)cap * 4;
+        lw.st_sm = (uint32_t *)(chain_lds + at); at += (size_t)cap * 4;
+        lw.cnodes = (CNode *)(chain_lds + at); at += (size_t)(cap / 4 + 2) * sizeof(CNode);
+        lw.nx = (int16_t *)(chain_lds + at); at += (size_t)cap * 2;
+        lw.ord16 = (int16_t *)(chain_lds + at);
+        st_cut = (CutT *)lw.ord16;
+        lw.ch = nullptr; lw.nodes = nullptr; lw.sd = nullptr; lw.ord = nullptr;
+        lw.staged = false;
+    } else {
         size_t at = 0;
         lw.ch = (WChain *)(chain_lds + at); at += (size_t)cap * sizeof(WChain);
         lw.nodes = (BtNode *)(chain_lds + at); at += (size_t)(cap / 4 + 2) * sizeof(BtNode);
@@ -818,6 +983,7 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
         lw.st_rid = (int32_t *)(chain_lds + at); at += (size_t)cap * 4;
         lw.st_sm = (uint32_t *)(chain_lds + at); at += (size_t)cap * 4;
         st_cut = (int32_t *)(chain_lds + at);
+        lw.cch = nullptr; lw.cnodes = nullptr; lw.nx = nullptr; lw.ord16 = nullptr;
         lw.staged = false;
     }
     const int64_t n_heavy = *n_heavy_p;
@@ -841,11 +1007,11 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
                 const int64_t so = smem_off[r];
                 const int64_t base = sa_off[so];
                 const int n_sa = (int)(sa_off[so + n_sm] - base);
-                if (n_sa > 0 && n_sa <= cap) {
+                if (n_sa > 0 && n_sa <= cap && (!CPT || n_sm <= cap)) {      // (CPT: a read that is not staged is chained on its global slices)
                     for (int i = lane; i < n_sm; i += 64) {
                         const uint32_t m = smems[so + i].m, n1 = smems[so + i].n + 1;
                         lw.st_sm[i] = (m & 0x7fffu) | (n1 & 0xffffu) << 15 | (smems[so + i].s > o.max_occ ? 1u << 31 : 0u);
-                        st_cut[i] = (int32_t)(sa_off[so + i + 1] - base);          // seeds of SMEM i end here
+                        st_cut[i] = (CutT)(sa_off[so + i + 1] - base);            // seeds of SMEM i end here
                     }
                     chain_wave_sync();
                     for (int t = lane; t < n_sa; t += 64) {
@@ -869,19 +1035,28 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
             __shared__ DeferFinish df;
             if (lane == 0) {
                 df.valid = 0;
-                chain_one_read<false>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
-                                      seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap, nullptr, nullptr, nullptr, &df);
+                chain_one_read<false, CPT>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
+                                           seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap, nullptr, nullptr, nullptr, &df);
             }
             flt_sync();
             if (df.valid) {
                 const DeferFinish d = df;
-                chain_finish_coop(o, d, lane, chn, seeds_out, seed_owner, n_chain_out, n_reg_out);
+                bool done = false;
+                if constexpr (CPT) {
+                    if (d.compact) {
+                        const CSeeds sdc = { lw.st_rbeg, lw.st_ql, (int16_t *)d.sd };
+                        chain_finish_coop_on(o, d.r, d.n, d.base, d.frac_rep, (CChain *)d.ch, sdc, (int16_t *)d.ord, (int16_t *)d.kept, lane, chn, seeds_out,
+                                             seed_owner, n_chain_out, n_reg_out);
+                        done = true;
+                    }
+                }
+                if (!done) chain_finish_coop(o, d, lane, chn, seeds_out, seed_owner, n_chain_out, n_reg_out);
             }
             flt_sync();
           }
         } else if (mine && lane == 0)
-            chain_one_read<false>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
-                                  seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap);
+            chain_one_read<false, CPT>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
+                                       seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap);
     }
 }
 
@@ -1435,7 +1610,9 @@ int bm2_launch_chain_finish(bm2_ctx *c, const ChainParams &o, int n_reads, const
     return bm2_check(hipGetLastError(), "k_chain_finish launch");
 }
 
-size_t bm2_chain_lds_bytes(int cap, int stage) {      // working set (chains, seeds, order, B-tree nodes) + staged inputs (24 bytes per seed)
+size_t bm2_chain_lds_bytes(int cap, int stage, int compact = 0) {      // working set (chains, seeds, order, B-tree nodes) + staged inputs (24 bytes per seed)
+    // compact (with staging only): chains 40, successor 2, order / SMEM cuts 2, staged inputs 20 per seed, nodes of 40 bytes -- the carving of k_chain_heavy<.., true>
+    if (compact && stage) return (size_t)cap * (sizeof(CChain) + 2 + 2 + 20) + (size_t)(cap / 4 + 2) * sizeof(CNode) + 16;
     return (size_t)cap * (sizeof(WChain) + sizeof(WSeed) + 4) + (size_t)(cap / 4 + 2) * sizeof(BtNode) + 16 + (stage ? (size_t)cap * 24 + 8 : 0);
 }
 
@@ -1481,10 +1658,17 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
         const int last_cap = stage ? 1000 : 1184;                 // (the last tier fills a CU's 160 KB of LDS)
         const int caps[5] = { 64, 128, 256, 512, last_cap };
         const int n_tiers = 5;
-        const int wpe = bm2_knob("BM2_CHAIN_HEAVY_WPE", 3);
-        auto k_heavy = coop ? (wpe >= 4 ? k_chain_heavy<true, 4> : wpe == 3 ? k_chain_heavy<true, 3> : k_chain_heavy<true, 2>)
-                            : (wpe >= 4 ? k_chain_heavy<false, 4> : wpe == 3 ? k_chain_heavy<false, 3> : k_chain_heavy<false, 2>);
-        { const int which = (coop ? 2 : 0) + 8 * (wpe >= 4 ? 2 : wpe == 3 ? 1 : 0);        // (one flag per instantiation: the limit is a property of the kernel)
+        // (4 since the compact LDS form: the tiers are no longer bound by LDS but by the wavefronts the registers leave room for -- sweep in pipeline.hip at BM2_HEAVY_SA)
+        const int wpe = bm2_knob("BM2_CHAIN_HEAVY_WPE", 4);
+        // BM2_CHAIN_LDS_COMPACT: the tiers keep a staged read's records in the compact form (chain_dev.h; 74 instead of 156 bytes of LDS per seed); 0, or no staging: the old layout
+        const int compact = stage && bm2_knob("BM2_CHAIN_LDS_COMPACT", 1);
+        auto k_heavy_old = coop ? (wpe >= 4 ? k_chain_heavy<true, 4, false> : wpe == 3 ? k_chain_heavy<true, 3, false> : k_chain_heavy<true, 2, false>)
+                                : (wpe >= 4 ? k_chain_heavy<false, 4, false> : wpe == 3 ? k_chain_heavy<false, 3, false> : k_chain_heavy<false, 2, false>);
+        auto k_heavy_cpt = coop ? (wpe >= 4 ? k_chain_heavy<true, 4, true> : wpe == 3 ? k_chain_heavy<true, 3, true> : k_chain_heavy<true, 2, true>)
+                                : (wpe >= 4 ? k_chain_heavy<false, 4, true> : wpe == 3 ? k_chain_heavy<false, 3, true> : k_chain_heavy<false, 2, true>);
+        auto k_heavy = compact ? k_heavy_cpt : k_heavy_old;
+        { const int which = compact ? 20 + (coop ? 1 : 0) + 2 * (wpe >= 4 ? 2 : wpe == 3 ? 1 : 0)      // (one flag per instantiation: the limit is a property of the kernel)
+                                    : (coop ? 2 : 0) + 8 * (wpe >= 4 ? 2 : wpe == 3 ? 1 : 0);
           const int rc_a = bm2_raise_lds_limit(c, which, (const void *)k_heavy, coop ? 160 * 1024 - 256 : 160 * 1024);       // (the cooperative one's static record rides on top of the dynamic LDS)
           if (rc_a) return rc_a; }
         // reads with more seeds than the largest tier holds: a launch of their own where they are the norm (long reads), otherwise the last tier's
@@ -1499,7 +1683,7 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
         for (int t = 0; t < n_tiers; t++) {
             if (caps[t] <= lo || caps[t] > tier_max) continue;
             hipStream_t sk = c->side_stream[2 + t];
-            const size_t lds = bm2_chain_lds_bytes(caps[t], stage);
+            const size_t lds = bm2_chain_lds_bytes(caps[t], stage, compact);
             const int per_cu_max = bm2_knob("BM2_CHAIN_WAVES_PER_CU", 16);
             int per_cu = (int)(160 * 1024 / lds); if (per_cu < 1) per_cu = 1; if (per_cu > per_cu_max) per_cu = per_cu_max;
             (void)hipStreamWaitEvent(sk, c->ev_fork, 0);
@@ -1557,7 +1741,7 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
                 }
             } else {
                 const int per_cu = bm2_knob("BM2_CHAIN_OVF_WAVES_PER_CU", 32);
-                hipLaunchKernelGGL(k_heavy, dim3(c->n_cu * per_cu), dim3(64), bm2_chain_lds_bytes(0, 0), sk, c->ix, o, n_reads, len, smems, smem_cnt, smem_off, sa_off,
+                hipLaunchKernelGGL(k_heavy_old /* no LDS: nothing to compact */, dim3(c->n_cu * per_cu), dim3(64), bm2_chain_lds_bytes(0, 0), sk, c->ix, o, n_reads, len, smems, smem_cnt, smem_off, sa_off,
                                    sa_coord, wchain, wseed, nodes, order, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, n_chain0_out, perm,
                                    n_heavy_dev, n_sa_read, lo, 0, 1, item_cur + CHAIN_CUR_SLOTS, 0, clk);
             }

@@ -21,5 +21,24 @@ struct BtNode {                      // kbnode_t with t = 5: up to 9 keys (chain
     int32_t is_internal, n, pad;
 };
 
+// ---- the COMPACT form of the same records: what k_chain_heavy keeps in LDS for a read whose inputs are staged there (chain.hip: "compact form").
+// Every index is at most the tier's capacity (<= 1184), a query position has 15 bits and a seed length 16 (they already travel so in st_ql): 16-bit
+// fields throughout, no padding.  Field NAMES are those of the records above, so the chaining code is written once over either form.
+struct CChain {                      // WChain in 40 bytes
+    int64_t pos, last_rbeg;
+    int32_t rid, w;
+    int16_t first_qbeg, last_qbeg; uint16_t last_len; int16_t n;
+    int16_t head, tail, first; uint8_t is_alt, kept;
+};
+struct CNode {                       // BtNode in 40 bytes: no kpos -- the chains sit in the same LDS, a probe reads ch[key].pos there
+    int16_t key[9];
+    int16_t ptr[10];
+    uint8_t is_internal, n;
+};
+struct CSeeds {                      // WSeed without a record: seed t IS the staged seed t (st_rbeg / st_ql), all that is kept is its successor in the chain
+    const int64_t *rbeg; const uint32_t *ql; int16_t *next;
+};
+static_assert(sizeof(CChain) == 40 && sizeof(CNode) == 40, "the LDS carving of k_chain_heavy counts on these");
+
 // where k_chain_finish's outputs go when the chaining kernel's lane writes them itself (chain.hip: chain_finish_one)
 struct FinishOut { const int32_t *len; int32_t *srt_out, *reg_seed, *reg_chain; };

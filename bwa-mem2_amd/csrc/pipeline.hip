@@ -367,8 +367,14 @@ static int batch_run_one(bm2_ctx *c, const bm2_opt *opt, StageGate *gate = nullp
     const int perm_mode_pf = bm2_knob("BM2_PERM_MODE_PF", 0);   // post-filter: read order
     // reads with more SA coordinates go to k_chain_heavy (round 3's sweep: 40 -> 13.6 ms, 100 -> 12.1 ms; with the lane kernel's reads in classes and the chains'
     // extension tasks built by its lanes -- round 6 -- the two sides of the stage end together at 72..80: 100 -> 9.0-9.1 ms, 90 -> 8.7, 80 -> 7.9-8.6, 72 -> 8.3,
-    // 64 -> 8.5, 56 -> 8.8, 48 -> 9.1, 120 -> 9.3; profiles/r06ao_*, r06ap_*)
-    const int thr_sa = bm2_knob("BM2_HEAVY_SA", 80);
+    // 64 -> 8.5, 56 -> 8.8, 48 -> 9.1, 120 -> 9.3; profiles/r06ao_*, r06ap_*.
+    // With the tiers' records in the compact LDS form (74 instead of 156 bytes per seed: twice the seed-rich reads in flight per CU) the tiers can take more of
+    // k_chain's longest classes.  One process, five steps per candidate, regs of every candidate equal to the default's (profiles/chain_lds_compact_ab.json),
+    // stage in ms at BM2_HEAVY_SA = 32 / 40 / 48 / 56 / 64 / 72 / 80:
+    //   BM2_CHAIN_HEAVY_WPE 3, BM2_CHAIN_WAVES_PER_CU 16: 6.21 6.08 6.12 6.12 6.86 6.27 6.80     WPE 3, 24 per CU: 6.23 6.20 6.15 6.16 6.66 6.33 6.78
+    //   WPE 4, 16 per CU:                                 5.65 5.61 5.64 5.56 5.82 6.18 6.76     WPE 4, 24 per CU: 5.93 5.59 5.76 5.52 6.03 6.19 6.72
+    // and between them 80 / WPE 3 / 16 on the compact form 6.70-6.74, on the old layout 7.3-7.9 (at 80: 7.9-8.2).  56 with four wavefronts per SIMD; 24 per CU buys nothing.)
+    const int thr_sa = bm2_knob("BM2_HEAVY_SA", 56);
     const int64_t *n_heavy_chain = nullptr;                      // set when the permutation lists the seed-rich reads first: k_chain_heavy takes them
     const int chain_heavy = bm2_knob("BM2_CHAIN_HEAVY", 1);
     if (perm_mode == 5) { if ((rc = bm2_partition_by_class(c, n, (const int32_t *)b->n_sa_read.p, thr_sa, (int32_t *)b->perm.p, b->part_tmp, b->scan_tmp, chain_heavy ? &n_heavy_chain : nullptr))) return rc; }

@@ -31,6 +31,10 @@ GRID = [   # (name, candidates): a candidate is a dict of knobs set together; th
     ("chaining AB: the tiers' knobs, the default measured between the candidates", [{}, {"BM2_CHAIN_HEAVY_WPE": 2}, {"BM2_PERM_MODE": 5}, {"BM2_CHAIN_WAVES_PER_CU": 8}, {"BM2_HEAVY_SA": 80}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_CHAIN_COOP_FLT": 1}, {"BM2_PERM_MODE": 4}, {"BM2_CHAIN_MAIN_SIDE": 1}, {"BM2_CHAIN_HEAVY_WPE": 2, "BM2_CHAIN_WAVES_PER_CU": 8}, {"BM2_CHAIN_STAGE": 1}, {"BM2_CHAIN_HEAVY_WPE": 2, "BM2_CHAIN_TIER_MAX": 512}, {"BM2_CHAIN_FUSE_FINISH": 1}, {"BM2_CHAIN_HEAVY_WPE": 2, "BM2_PERM_MODE": 4}]),
     ("chaining AB2: reads beyond 512 seeds to the island kernel, the default measured between", [{}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_CHAIN_COOP_FLT": 1}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_CHAIN_STAGE": 1}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_PERM_MODE": 5}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_HEAVY_SA": 80}, {"BM2_CHAIN_TIER_MAX": 512}, {"BM2_CHAIN_MAIN_SIDE": 1}, {"BM2_CHAIN_TIER_MAX": 256}, {"BM2_CHAIN_FUSE_FINISH": 1}, {"BM2_CHAIN_TIER_MAX": 256}]),
     ("AB3: seeding / extension knobs, the default measured between", [{}, {"BM2_BWD_HEAVY_WG": 8}, {"BM2_PERM_MODE": 5}, {"BM2_BWD_EXPORT_AGE": 160}, {"BM2_HEAVY_SA": 80}, {"BM2_BWD_HEAVY_WG": 8}, {"BM2_CHAIN_STAGE": 1}, {"BM2_BWD_EXPORT_AGE": 160}, {"BM2_CHAIN_COOP_FLT": 1}, {"BM2_EXT_PEND_DIV": 6}, {"BM2_CHAIN_MAIN_SIDE": 1}, {"BM2_EXT_PEND_DIV": 6}, {"BM2_CHAIN_FUSE_FINISH": 1}, {"BM2_BWD_HEAVY_WG": 8, "BM2_BWD_EXPORT_AGE": 160}, {"BM2_CHAIN_FINISH_WAVE": 1}, {"BM2_BWD_HEAVY_WG": 8, "BM2_BWD_EXPORT_AGE": 160}]),
+    ("chain compact LDS: threshold x wavefronts per SIMD x wavefronts per CU, the default and the old layout measured between",
+     [{}] + [c for wpe in (3, 4) for wcu in (16, 24)
+             for c in [dict(BM2_HEAVY_SA=t, BM2_CHAIN_HEAVY_WPE=wpe, BM2_CHAIN_WAVES_PER_CU=wcu) for t in (32, 40, 48, 56, 64, 72, 80)] +
+                      [{}, {"BM2_CHAIN_LDS_COMPACT": 0}, {"BM2_CHAIN_LDS_COMPACT": 0, "BM2_HEAVY_SA": 80}]]),
     ("chain clock", [{}, {"BM2_CHAIN_CLOCK": 1}]),
     ("chain staging", [{}, {"BM2_CHAIN_STAGE": 1}]),
     ("chain heavy threshold", [{}, {"BM2_HEAVY_SA": 100}, {"BM2_HEAVY_SA": 72}, {"BM2_HEAVY_SA": 64}]),

@@ -770,7 +770,8 @@ struct ChainWork {
 // mem_chain_seeds + mem_chain_flt for read r.  LIGHT: the lane-per-read kernel (global slices); otherwise the caller offers LDS
 // for up to lds_cap seeds in `lw`.  CPT (k_chain_heavy with staging): that LDS holds the compact form of the records, for a read the wavefront has staged;
 // any other read of such a launch (the last tier's beyond its cap) is chained on its global slices in the records they have always had.
-template <bool LIGHT, bool CPT = false>
+// FIN: `fo` is honoured -- the lane that emits the read's chains builds their extension tasks as well (k_chain's lanes, k_chain_group's workers).
+template <bool LIGHT, bool CPT = false, bool FIN = LIGHT>
 static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, int r, int n_reads, const int32_t *__restrict__ len,
                                       const bm2_smem_t *__restrict__ smems, const int32_t *__restrict__ smem_cnt,
                                       const int64_t *__restrict__ smem_off, const int64_t *__restrict__ sa_off,
@@ -779,7 +780,7 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
                                       int32_t *n_chain0_out, int heavy_thr, const ChainWork *lw, int lds_cap, const IslSeed *ist = nullptr,
                                       const IslHash *isl_hash = nullptr, const int32_t *isl_slot = nullptr,
                                       DeferFinish *defer = nullptr /* !LIGHT: leave mem_chain_flt's walk and the output to the caller's wavefront */,
-                                      const FinishOut *fo = nullptr /* LIGHT: the lane also builds the read's extension tasks (k_chain_finish's part) */) {
+                                      const FinishOut *fo = nullptr /* FIN: the lane also builds the read's extension tasks (k_chain_finish's part) */) {
     const int n_sm = smem_cnt[r];
     const long long t_enter = (!LIGHT && lw && lw->clk) ? wall_clock64() : 0;
     n_chain_out[r] = 0; n_reg_out[r] = 0;          // (k_chain never gets here with a read it leaves to k_chain_heavy: one writer per read)
@@ -887,7 +888,7 @@ static __device__ void chain_one_read(const DevIndex &ix, const ChainParams &o, 
         defer->valid = 1;
         return;
     }
-    chain_finish_read(o, r, ch, sd, ord, kept, k, base, frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, &ix, LIGHT ? fo : nullptr);
+    chain_finish_read(o, r, ch, sd, ord, kept, k, base, frac_rep, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, &ix, FIN ? fo : nullptr);
     if (!LIGHT && lw && lw->clk) atomicAdd(lw->clk + 2, (unsigned long long)(wall_clock64() - t_walk));
     };
     if constexpr (CPT) {
@@ -916,11 +917,14 @@ k_chain(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict__ len
         const int64_t *__restrict__ sa_coord, WChain *wchain, WSeed *wseed, BtNode *nodes, int32_t *order,
         DevChain *chn, DevSeed *seeds_out, int32_t *seed_owner,
         int32_t *n_chain_out, int32_t *n_reg_out, int32_t *n_chain0_out, const int32_t *__restrict__ perm, int heavy_thr,
-        const int32_t *__restrict__ n_sa_read, FinishOut fo /* srt_out == nullptr: k_chain_finish does every read */) {
+        const int32_t *__restrict__ n_sa_read, FinishOut fo /* srt_out == nullptr: k_chain_finish does every read */,
+        int grp_lo, int grp_hi /* grp_hi > 0: the reads with grp_lo < SA coordinates <= grp_hi are k_chain_group's */) {
     const int tix = blockIdx.x * blockDim.x + threadIdx.x;
     if (tix >= n_reads) return;
-    if (heavy_thr >= 0 && n_sa_read[perm[tix]] > heavy_thr) return;          // a whole wavefront takes this read (k_chain_heavy)
-    chain_one_read<true>(ix, o, perm[tix], n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
+    const int r = perm[tix], ns = n_sa_read[r];
+    if (heavy_thr >= 0 && ns > heavy_thr) return;                            // a whole wavefront takes this read (k_chain_heavy)
+    if (ns > grp_lo && ns <= grp_hi) return;                                 // a lane group takes it (k_chain_group)
+    chain_one_read<true>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
                          seed_owner, n_chain_out, n_reg_out, n_chain0_out, heavy_thr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, fo.srt_out ? &fo : nullptr);
 }
 
@@ -928,6 +932,67 @@ static __device__ __forceinline__ void chain_wave_sync() {      // lanes of one 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The compact working set of one read (chain_dev.h) carved from bm2_chain_lds_bytes(cap, 1, 1) bytes of LDS at p: a wavefront's (k_chain_heavy<.., true>) or a
+// lane group's (k_chain_group).  Returns where the staging keeps its SMEM cuts: the order array, which the walk needs only afterwards.
+static __device__ __forceinline__ uint16_t *chain_carve_compact(uint8_t *p, int cap, ChainWork &lw) {
+    size_t at = 0;                                                // (widest first: every array starts at a multiple of its element size)
+    lw.cch = (CChain *)(p + at); at += (size_t)cap * sizeof(CChain);
+    lw.st_rbeg = (int64_t *)(p + at); at += (size_t)cap * 8;
+    lw.st_ql = (uint32_t *)(p + at); at += (size_t)cap * 4;
+    lw.st_rid = (int32_t *)(p + at); at += (size_t)cap * 4;
+    lw.st_sm = (uint32_t *)(p + at); at += (size_t)cap * 4;
+    lw.cnodes = (CNode *)(p + at); at += (size_t)(cap / 4 + 2) * sizeof(CNode);
+    lw.nx = (int16_t *)(p + at); at += (size_t)cap * 2;
+    lw.ord16 = (int16_t *)(p + at);
+    lw.ch = nullptr; lw.nodes = nullptr; lw.sd = nullptr; lw.ord = nullptr;
+    lw.staged = false;
+    return (uint16_t *)lw.ord16;
+}
+
+// Staging: the inputs of read r that do not depend on the walk, fetched into the LDS arrays of `lw` by nl adjacent lanes of a wavefront, of which the caller
+// is number l -- a whole wavefront (0..63 of 64: k_chain_heavy) or a lane group (k_chain_group).  Per SMEM its query span and where its seeds end (st_cut);
+// per seed its SMEM by bisection of the cuts, the reference position, and the contig bns_intv2rid gives with its ALT flag.
+// EVERY lane of the wavefront calls this together -- the two chain_wave_sync() are the wavefront's --; `want` is false in the lanes whose group has
+// nothing to stage.  lw.staged tells whether the read fits (at most cap seeds and, CPT, cap SMEMs: a read that is not staged is chained on its global slices).
+template <bool CPT, class CutT>
+static __device__ __forceinline__ void chain_stage_read(const DevIndex &ix, const ChainParams &o, bool want, int r, int cap, const bm2_smem_t *__restrict__ smems,
+                                                        const int32_t *__restrict__ smem_cnt, const int64_t *__restrict__ smem_off,
+                                                        const int64_t *__restrict__ sa_off, const int64_t *__restrict__ sa_coord, ChainWork &lw, CutT *st_cut,
+                                                        int l, int nl) {
+    int n_sm = 0, n_sa = 0;
+    int64_t so = 0, base = 0;
+    bool fits = false;
+    if (want) {
+        n_sm = smem_cnt[r];
+        if (n_sm > 0) {
+            so = smem_off[r];
+            base = sa_off[so];
+            n_sa = (int)(sa_off[so + n_sm] - base);
+            fits = n_sa > 0 && n_sa <= cap && (!CPT || n_sm <= cap);
+        }
+    }
+    if (fits)
+        for (int i = l; i < n_sm; i += nl) {
+            const uint32_t m = smems[so + i].m, n1 = smems[so + i].n + 1;
+            lw.st_sm[i] = (m & 0x7fffu) | (n1 & 0xffffu) << 15 | (smems[so + i].s > o.max_occ ? 1u << 31 : 0u);
+            st_cut[i] = (CutT)(sa_off[so + i + 1] - base);            // seeds of SMEM i end here
+        }
+    chain_wave_sync();
+    if (fits)
+        for (int t = l; t < n_sa; t += nl) {
+            int a = 0, b = n_sm - 1;                                  // the seed's SMEM: first i with st_cut[i] > t
+            while (a < b) { const int mid = (a + b) >> 1; if (st_cut[mid] > t) b = mid; else a = mid + 1; }
+            const uint32_t sm = lw.st_sm[a];
+            const int qbeg = (int)(sm & 0x7fffu), slen = (int)((sm >> 15) & 0xffffu) - qbeg;
+            const int64_t rbeg = sa_coord[base + t];
+            const int rid = intv2rid(ix, rbeg, rbeg + slen);
+            const uint32_t alt = rid >= 0 && ix.ann_is_alt[rid] ? 1u : 0u;
+            lw.st_rbeg[t] = rbeg; lw.st_ql[t] = (uint32_t)qbeg | (uint32_t)slen << 15 | alt << 31; lw.st_rid[t] = rid;
+        }
+    chain_wave_sync();
+    lw.staged = fits;
 }
 
 // Seed-rich reads, ONE READ PER WAVEFRONT.  Chaining is sequential per read by definition (every seed meets the B-tree the earlier
@@ -959,18 +1024,7 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
     typedef typename std::conditional<CPT, uint16_t, int32_t>::type CutT;      // (a cut is a seed count of the read: at most cap)
     CutT *st_cut = nullptr;
     if constexpr (CPT) {
-        size_t at = 0;                                                // (widest first: every array starts at a multiple of its element size)
-        lw.cch = (CChain *)(chain_lds + at); at += (size_t)cap * sizeof(CChain);
-        lw.st_rbeg = (int64_t *)(chain_lds + at); at += (size_t)cap * 8;
-        lw.st_ql = (uint32_t *)(chain_lds + at); at += (size_t)cap * 4;
-        lw.st_rid = (int32_t *)(chain_lds + at); at += (size_t)cap * 4;
-        lw.st_sm = (uint32_t *)(chain_lds + at); at += (size_t)cap * 4;
-        lw.cnodes = (CNode *)(chain_lds + at); at += (size_t)(cap / 4 + 2) * sizeof(CNode);
-        lw.nx = (int16_t *)(chain_lds + at); at += (size_t)cap * 2;
-        lw.ord16 = (int16_t *)(chain_lds + at);
-        st_cut = (CutT *)lw.ord16;
-        lw.ch = nullptr; lw.nodes = nullptr; lw.sd = nullptr; lw.ord = nullptr;
-        lw.staged = false;
+        st_cut = (CutT *)chain_carve_compact(chain_lds, cap, lw);
     } else {
         size_t at = 0;
         lw.ch = (WChain *)(chain_lds + at); at += (size_t)cap * sizeof(WChain);
@@ -1001,34 +1055,8 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
         // not depend on the walk: the 64 lanes fetch them for 64 seeds at a time into LDS first.
         lw.staged = false;
         const long long t_stage = clk && mine ? wall_clock64() : 0;
-        if (mine && stage && ns <= cap) {
-            const int n_sm = smem_cnt[r];
-            if (n_sm > 0) {
-                const int64_t so = smem_off[r];
-                const int64_t base = sa_off[so];
-                const int n_sa = (int)(sa_off[so + n_sm] - base);
-                if (n_sa > 0 && n_sa <= cap && (!CPT || n_sm <= cap)) {      // (CPT: a read that is not staged is chained on its global slices)
-                    for (int i = lane; i < n_sm; i += 64) {
-                        const uint32_t m = smems[so + i].m, n1 = smems[so + i].n + 1;
-                        lw.st_sm[i] = (m & 0x7fffu) | (n1 & 0xffffu) << 15 | (smems[so + i].s > o.max_occ ? 1u << 31 : 0u);
-                        st_cut[i] = (CutT)(sa_off[so + i + 1] - base);            // seeds of SMEM i end here
-                    }
-                    chain_wave_sync();
-                    for (int t = lane; t < n_sa; t += 64) {
-                        int a = 0, b = n_sm - 1;                                  // the seed's SMEM: first i with st_cut[i] > t
-                        while (a < b) { const int mid = (a + b) >> 1; if (st_cut[mid] > t) b = mid; else a = mid + 1; }
-                        const uint32_t sm = lw.st_sm[a];
-                        const int qbeg = (int)(sm & 0x7fffu), slen = (int)((sm >> 15) & 0xffffu) - qbeg;
-                        const int64_t rbeg = sa_coord[base + t];
-                        const int rid = intv2rid(ix, rbeg, rbeg + slen);
-                        const uint32_t alt = rid >= 0 && ix.ann_is_alt[rid] ? 1u : 0u;
-                        lw.st_rbeg[t] = rbeg; lw.st_ql[t] = (uint32_t)qbeg | (uint32_t)slen << 15 | alt << 31; lw.st_rid[t] = rid;
-                    }
-                    chain_wave_sync();
-                    lw.staged = true;
-                }
-            }
-        }
+        if (mine && stage && ns <= cap)
+            chain_stage_read<CPT>(ix, o, true, r, cap, smems, smem_cnt, smem_off, sa_off, sa_coord, lw, st_cut, lane, 64);
         if (clk && mine && lane == 0) { atomicAdd(clk, (unsigned long long)(wall_clock64() - t_stage)); atomicAdd(clk + 3, 1ULL); atomicAdd(clk + 4, (unsigned long long)ns); }
         if constexpr (COOP) {
           if (mine) {                                              // (`mine` is the same in every lane)
@@ -1057,6 +1085,45 @@ k_chain_heavy(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict
         } else if (mine && lane == 0)
             chain_one_read<false, CPT>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
                                        seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap);
+    }
+}
+
+// Light reads, ONE READ PER GROUP OF G ADJACENT LANES (BM2_CHAIN_GROUP): the middle between k_chain -- a lane per read on its global slices, ~1000 dependent
+// global accesses for a read of nine seeds -- and k_chain_heavy, which spends a wavefront on a read.  A wavefront holds 64 / G reads; every group owns
+// bm2_chain_lds_bytes(cap, 1, 1) bytes of the workgroup's LDS, carved as k_chain_heavy<.., true> carves a wavefront's; the G lanes stage their read's inputs
+// (chain_stage_read), then the group's first lane walks them in the compact form, emits the read's chains and -- with `fo` -- builds their extension tasks,
+// as k_chain's lane does.  A read that fails the staging guard is chained by that lane on its global slices.
+// One launch per seed-count class of the class partition: [cls_pos[cls * n_reads], cls_pos[(cls + 1) * n_reads]) of `perm`, the bounds read here; the groups of
+// the grid take that range in turns (neighbouring groups, neighbouring reads).  Of it a read is this kernel's when grp_lo < its SA coordinates <= grp_hi --
+// the test k_chain skips it by: one writer per read.
+template <int G>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_chain_group(DevIndex ix, ChainParams o, int n_reads, const int32_t *__restrict__ len, const bm2_smem_t *__restrict__ smems,
+              const int32_t *__restrict__ smem_cnt, const int64_t *__restrict__ smem_off, const int64_t *__restrict__ sa_off,
+              const int64_t *__restrict__ sa_coord, WChain *wchain, WSeed *wseed, BtNode *nodes, int32_t *order,
+              DevChain *chn, DevSeed *seeds_out, int32_t *seed_owner, int32_t *n_chain_out, int32_t *n_reg_out, int32_t *n_chain0_out,
+              const int32_t *__restrict__ perm, const int64_t *__restrict__ cls_pos, int cls, const int32_t *__restrict__ n_sa_read,
+              int grp_lo, int grp_hi, int cap, FinishOut fo /* srt_out == nullptr: k_chain_finish does every read */) {
+    static_assert(G >= 1 && G <= 64 && (G & (G - 1)) == 0, "a group is a power of two of adjacent lanes");
+    extern __shared__ __attribute__((aligned(16))) uint8_t chain_lds[];
+    const int lane = threadIdx.x, l = lane & (G - 1), grp = lane / G;
+    constexpr int PER_WAVE = 64 / G;
+    const size_t per_group = (size_t)cap * (sizeof(CChain) + 2 + 2 + 20) + (size_t)(cap / 4 + 2) * sizeof(CNode) + 16;      // bm2_chain_lds_bytes(cap, 1, 1)
+    ChainWork lw;
+    uint16_t *st_cut = chain_carve_compact(chain_lds + (size_t)grp * per_group, cap, lw);
+    const int64_t beg = cls_pos[(int64_t)cls * n_reads], end = cls_pos[(int64_t)(cls + 1) * n_reads];
+    const int64_t step = (int64_t)gridDim.x * PER_WAVE;
+    for (int64_t i0 = beg + (int64_t)blockIdx.x * PER_WAVE; i0 < end; i0 += step) {      // (the same trip count in every lane: the staging's barriers are the wavefront's)
+        const int64_t i = i0 + grp;
+        int r = 0;
+        bool mine = false;
+        if (i < end) { r = perm[i]; const int ns = n_sa_read[r]; mine = ns > grp_lo && ns <= grp_hi; }
+        chain_stage_read<true>(ix, o, mine, r, cap, smems, smem_cnt, smem_off, sa_off, sa_coord, lw, st_cut, l, G);
+        if (mine && l == 0)
+            chain_one_read<false, true, true>(ix, o, r, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out,
+                                              seed_owner, n_chain_out, n_reg_out, n_chain0_out, -1, &lw, cap, nullptr, nullptr, nullptr, nullptr,
+                                              fo.srt_out ? &fo : nullptr);
+        chain_wave_sync();                                           // (the next round's staging writes the LDS this walk has read)
     }
 }
 
@@ -1625,10 +1692,22 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
                      int32_t *isl_cut /* scratch of the island kernel: one int per SA coordinate */,
                      const int32_t *isl_order /* or NULL: every read, the seed-richest first -- the island kernel's longest reads start first */,
                      int32_t *isl_serial /* or NULL: one int per read (all -1), the list of reads k_chain_islands leaves to k_chain_serial */,
-                     const FinishOut *fuse /* or NULL.  Set (no read of the batch can meet the seed filter): k_chain's lanes do k_chain_finish's part for their reads */) {
+                     const FinishOut *fuse /* or NULL.  Set (no read of the batch can meet the seed filter): k_chain's lanes do k_chain_finish's part for their reads */,
+                     const int64_t *cls_pos /* or NULL.  Set: `perm` is the class partition's and this is its scan (class k starts at cls_pos[k * n_reads]), and
+                                               no read of the batch meets the seed filter or the island kernel: the lane-group launches may take light reads */) {
     if (n_reads <= 0) return BM2_OK;
     hipStream_t s = c->stream;
     const bool heavy = heavy_thr >= 0 && n_heavy_dev != nullptr;
+    // BM2_CHAIN_GROUP = G (0: off): the light reads with BM2_CHAIN_GROUP_MIN < SA coordinates <= min(64, heavy_thr) are chained by groups of G lanes on records
+    // staged in LDS (k_chain_group), one launch per class of the class partition; k_chain keeps the rest.  Measured (DESIGN.md section 6i,
+    // profiles/chain_group_ab.json): the classes up to 16 seeds do not repay staging at any G -- a CU's LDS holds 128-238 such reads against k_chain's 768 lanes --,
+    // the two seed-richest light classes do: G 8, lower bound 16, 16 wavefronts per CU and class: k_chain 5.3 -> 3.8 ms, the stage 6.8-7.4 -> 6.2-6.4 ms in six
+    // alternating bench processes each.
+    int grp_g = heavy && cls_pos && max_len < 1000 ? bm2_knob("BM2_CHAIN_GROUP", 8) : 0;
+    if (grp_g != 0 && grp_g != 2 && grp_g != 4 && grp_g != 8) { bm2_set_error("BM2_CHAIN_GROUP=%d: 0, 2, 4 or 8", grp_g); return BM2_EINVAL; }
+    const int grp_lo = bm2_knob("BM2_CHAIN_GROUP_MIN", 16) < 0 ? 0 : bm2_knob("BM2_CHAIN_GROUP_MIN", 16);
+    const int grp_hi = grp_g ? (heavy_thr < 64 ? heavy_thr : 64) : 0;
+    if (grp_hi <= grp_lo) grp_g = 0;
     if (heavy && bm2_side_streams(c)) return BM2_ENODEV;
     if (heavy) (void)hipEventRecord(c->ev_fork, s);
     // With the wavefront-per-read launches beside it, the lane-per-read kernel goes to a side stream of its own and the main stream only
@@ -1640,8 +1719,9 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
     if (main_side) (void)hipStreamWaitEvent(s_main, c->ev_fork, 0);
     hipLaunchKernelGGL(k_chain, dim3((n_reads + 127) / 128), dim3(128), 0, s_main, c->ix, o, n_reads, len, smems, smem_cnt,
                        smem_off, sa_off, sa_coord, wchain, wseed, nodes, order, chn, seeds_out, seed_owner,
-                       n_chain_out, n_reg_out, n_chain0_out, perm, heavy ? heavy_thr : -1, n_sa_read, fuse ? *fuse : FinishOut{ nullptr, nullptr, nullptr, nullptr });
-    int joined[BM2_CHAIN_TIERS + 4], n_joined = 0;
+                       n_chain_out, n_reg_out, n_chain0_out, perm, heavy ? heavy_thr : -1, n_sa_read, fuse ? *fuse : FinishOut{ nullptr, nullptr, nullptr, nullptr },
+                       grp_lo, grp_g ? grp_hi : 0);
+    int joined[BM2_CHAIN_TIERS + 9], n_joined = 0;
     if (main_side) { (void)hipEventRecord(c->ev_join[1], s_main); joined[n_joined++] = 1; }
     if (heavy) {
         // tiers by seed count (LDS per block follows the tier): the launches run beside the lane-per-read kernel and each other
@@ -1694,6 +1774,34 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
             (void)hipEventRecord(c->ev_join[2 + t], sk);
             joined[n_joined++] = 2 + t;
             lo = caps[t];
+        }
+        if (grp_g) {
+            // classes of bm2_partition_by_class (scan.hip: work_class) and the capacity a group's LDS gets for each: 2: 33..64, 3: 17..32, 4: 9..16, 5: 5..8, 6: 0..4
+            // seeds.  (Class 1, 65..heavy_thr, stays with k_chain: 32 groups of capacity 128 do not fit a CU's LDS.)  The classes a nine-seed read falls in
+            // are queued first.  Streams: the three spare tier slots, then 0 and 11, which chaining uses for long reads only.
+            // BM2_CHAIN_GROUP_CAP_MAX: capacities are clipped to it -- a read beyond it is chained by its group's first lane on its global slices (tests).
+            static const int g_cls[5] = { 4, 5, 3, 2, 6 }, g_lo[5] = { 8, 4, 16, 32, -1 }, g_hi[5] = { 16, 8, 32, 64, 4 }, g_cap[5] = { 16, 8, 32, 64, 8 }, g_stream[5] = { 7, 8, 9, 0, 11 };
+            const int cap_max = bm2_knob("BM2_CHAIN_GROUP_CAP_MAX", 64);
+            const int per_cu_max = bm2_knob("BM2_CHAIN_GROUP_WAVES_PER_CU", 16);
+            auto k_grp = grp_g == 2 ? k_chain_group<2> : grp_g == 4 ? k_chain_group<4> : k_chain_group<8>;
+            { const int rc_a = bm2_raise_lds_limit(c, grp_g == 2 ? 26 : grp_g == 4 ? 27 : 28, (const void *)k_grp, 160 * 1024); if (rc_a) return rc_a; }
+            const int per_wave = 64 / grp_g;
+            for (int k = 0; k < 5; k++) {
+                if (g_lo[k] >= grp_hi || g_hi[k] <= grp_lo) continue;      // (no read of the class is this kernel's)
+                int cap = g_cap[k] < cap_max ? g_cap[k] : cap_max; if (cap < 4) cap = 4;
+                const size_t lds = (size_t)per_wave * bm2_chain_lds_bytes(cap, 1, 1);
+                int per_cu = (int)(160 * 1024 / lds); if (per_cu < 1) per_cu = 1; if (per_cu > per_cu_max) per_cu = per_cu_max;
+                int64_t grid = (int64_t)c->n_cu * per_cu;
+                const int64_t need = ((int64_t)n_reads + per_wave - 1) / per_wave;
+                if (grid > need) grid = need;
+                hipStream_t sk = c->side_stream[g_stream[k]];
+                (void)hipStreamWaitEvent(sk, c->ev_fork, 0);
+                hipLaunchKernelGGL(k_grp, dim3((unsigned)grid), dim3(64), lds, sk, c->ix, o, n_reads, len, smems, smem_cnt, smem_off, sa_off, sa_coord, wchain, wseed,
+                                   nodes, order, chn, seeds_out, seed_owner, n_chain_out, n_reg_out, n_chain0_out, perm, cls_pos, g_cls[k], n_sa_read, grp_lo, grp_hi,
+                                   cap, fuse ? *fuse : FinishOut{ nullptr, nullptr, nullptr, nullptr });
+                (void)hipEventRecord(c->ev_join[g_stream[k]], sk);
+                joined[n_joined++] = g_stream[k];
+            }
         }
         // Reads with more seeds than the largest tier holds in LDS (long reads: ~12 k seeds per 10 kb read) walk their GLOBAL slices.  They
         // used to ride in the last tier -- whose blocks reserve a CU's whole LDS, so only one such walk ran per CU: 256 at a time, 5.1 s for

@@ -18,7 +18,7 @@ int bm2_launch_chain(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_
                      int32_t *seed_owner,
                      int32_t *n_chain_out, int32_t *n_reg_out, int32_t *n_chain0_out, const int32_t *perm,
                      int heavy_thr, const int64_t *n_heavy_dev, const int32_t *n_sa_read, unsigned long long *item_cur, int max_len, int32_t *isl_cut,
-                     const int32_t *isl_order, int32_t *isl_serial, const FinishOut *fuse);
+                     const int32_t *isl_order, int32_t *isl_serial, const FinishOut *fuse, const int64_t *cls_pos);
 int bm2_launch_chain_finish(bm2_ctx *c, const ChainParams &o, int n_reads, const int32_t *len, const int64_t *read_base,
                             const int32_t *n_chain, DevChain *chn, DevSeed *seeds_out, int32_t *srt_out, int32_t *reg_seed,
                             int32_t *reg_chain, int32_t *n_reg_out, const int32_t *perm, bool lanes_by_perm, const int32_t *n_sa_read, int done_thr, const int64_t *n_heavy_dev, int wave_thr);
@@ -341,14 +341,29 @@ static int batch_run_one(bm2_ctx *c, const bm2_opt *opt, StageGate *gate = nullp
     // mem_flt_chained_seeds thresholds (bwamem.cpp:484-490), evaluated on the host with the same libm the reference uses:
     // min_l = W ? 1.1f*W : 5.5f*log(l_query); active when !(min_l > 0.05f*l_query); min_HSP_score = (int)(a*min_l + .499)
     bool any_flt = false;
+    const bool verbose_host = getenv("BM2_VERBOSE") != nullptr;
+    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     {
+        // (once per DISTINCT read length -- a short-read batch has one or a handful, and a million log() calls sat between the SA look-up's launch and the chain
+        //  launches; the value is a function of the length alone and comes from the same libm call.  A batch whose lengths spread wider than its reads are
+        //  many -- long reads -- keeps the call per read.)
+        const double t_mh = verbose_host ? now_ms() : 0.;
         std::vector<int32_t> mh((size_t)n);
+        auto min_hsp_of = [&](int lq) -> int32_t {
+            const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log((double)lq);
+            if (lq > 0 && !(min_l > 0.05f * lq)) { const int32_t v = (int)(opt->a * min_l + .499); return v < 0 ? 0 : v; }
+            return -1;
+        };
+        const int tab_max = b->max_len;
+        const bool by_len = tab_max >= 0 && (int64_t)tab_max <= 4 * (int64_t)n + 1024;
+        std::vector<int32_t> tab(by_len ? (size_t)tab_max + 1 : 0, INT32_MIN);      // INT32_MIN: not computed yet (a value is -1 or >= 0)
         for (int i = 0; i < n; i++) {
             const int lq = b->h_len[i];
-            const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log((double)lq);
-            if (lq > 0 && !(min_l > 0.05f * lq)) { mh[i] = (int)(opt->a * min_l + .499); if (mh[i] < 0) mh[i] = 0; any_flt = true; }
-            else mh[i] = -1;
+            if (by_len && lq >= 0 && lq <= tab_max) { if (tab[lq] == INT32_MIN) tab[lq] = min_hsp_of(lq); mh[i] = tab[lq]; }
+            else mh[i] = min_hsp_of(lq);
+            if (mh[i] >= 0) any_flt = true;
         }
+        if (verbose_host) fprintf(stderr, "[chain] min_hsp of %d reads on the host %.2f ms\n", n, now_ms() - t_mh);
         if (any_flt) {
             if ((rc = bm2_reserve(b->min_hsp, (size_t)(n + 1) * 4))) return rc;
             if ((rc = bm2_reserve(b->seed_keep, ns))) return rc;
@@ -375,9 +390,10 @@ static int batch_run_one(bm2_ctx *c, const bm2_opt *opt, StageGate *gate = nullp
     //   WPE 4, 16 per CU:                                 5.65 5.61 5.64 5.56 5.82 6.18 6.76     WPE 4, 24 per CU: 5.93 5.59 5.76 5.52 6.03 6.19 6.72
     // and between them 80 / WPE 3 / 16 on the compact form 6.70-6.74, on the old layout 7.3-7.9 (at 80: 7.9-8.2).  56 with four wavefronts per SIMD; 24 per CU buys nothing.)
     const int thr_sa = bm2_knob("BM2_HEAVY_SA", 56);
+    const int64_t *cls_pos = nullptr;                            // the class partition's scan: class k of `perm` starts at cls_pos[k * n] (k_chain_group's launches read their bounds there)
     const int64_t *n_heavy_chain = nullptr;                      // set when the permutation lists the seed-rich reads first: k_chain_heavy takes them
     const int chain_heavy = bm2_knob("BM2_CHAIN_HEAVY", 1);
-    if (perm_mode == 5) { if ((rc = bm2_partition_by_class(c, n, (const int32_t *)b->n_sa_read.p, thr_sa, (int32_t *)b->perm.p, b->part_tmp, b->scan_tmp, chain_heavy ? &n_heavy_chain : nullptr))) return rc; }
+    if (perm_mode == 5) { if ((rc = bm2_partition_by_class(c, n, (const int32_t *)b->n_sa_read.p, thr_sa, (int32_t *)b->perm.p, b->part_tmp, b->scan_tmp, chain_heavy ? &n_heavy_chain : nullptr, &cls_pos))) return rc; }
     else if (perm_mode == 3 || perm_mode == 4) { if ((rc = bm2_partition_by_work(c, n, (const int32_t *)b->n_sa_read.p, thr_sa, (int32_t *)b->perm.p, b->part_tmp, b->scan_tmp, perm_mode == 4, perm_mode == 4 && chain_heavy ? &n_heavy_chain : nullptr))) return rc; }
     else if ((rc = bm2_perm_by_work(c, n, (const int32_t *)b->n_sa_read.p, (int32_t *)b->perm.p, (uint32_t *)b->perm_hist.p, perm_mode))) return rc;
     // long reads: the island kernel takes its reads by falling seed count (log2 classes), so that the few reads it has to chain serially --
@@ -411,7 +427,8 @@ static int batch_run_one(bm2_ctx *c, const bm2_opt *opt, StageGate *gate = nullp
                                (DevChain *)b->chn.p, (DevSeed *)b->seeds.p, (int32_t *)b->seed_owner.p,
                                (int32_t *)b->n_chain.p, (int32_t *)b->n_reg.p, (int32_t *)b->n_chain0.p, (const int32_t *)b->perm.p,
                                n_heavy_chain ? thr_sa : -1, n_heavy_chain, (const int32_t *)b->n_sa_read.p,
-                               (unsigned long long *)b->counters.p + 10, b->max_len, (int32_t *)b->srt.p, isl_order, isl_serial, fuse_finish ? &fin_out : nullptr))) return rc;      // counters[10..15]: work cursors of the tiers and of the overflow launch, [16]: reads listed for k_chain_serial (equal chain keys; [39] of them not staged), [38]: its work cursor
+                               (unsigned long long *)b->counters.p + 10, b->max_len, (int32_t *)b->srt.p, isl_order, isl_serial, fuse_finish ? &fin_out : nullptr,
+                               !any_flt && b->max_len < 1000 ? cls_pos : (const int64_t *)nullptr))) return rc;      // counters[10..15]: work cursors of the tiers and of the overflow launch, [16]: reads listed for k_chain_serial (equal chain keys; [39] of them not staged), [38]: its work cursor
     if (any_flt) {
         if ((rc = bm2_launch_seed_filter(c, cp, (const int8_t *)b->mat25.p, n, n_sa, (const uint8_t *)b->enc.p, (const int64_t *)b->off.p,
                                          (const int32_t *)b->len.p, (const int32_t *)b->min_hsp.p, (const int64_t *)b->read_base.p,

@@ -173,7 +173,8 @@ __global__ void __launch_bounds__(256) k_class_scatter(int n, const int32_t *__r
     if (i >= n) return;
     perm[pos[(int64_t)work_class(key[i], thr) * n + i]] = i;
 }
-int bm2_partition_by_class(bm2_ctx *c, int n, const int32_t *key, int thr, int32_t *perm, DevBuf &tmp, DevBuf &scan_tmp, const int64_t **n_heavy_dev) {
+int bm2_partition_by_class(bm2_ctx *c, int n, const int32_t *key, int thr, int32_t *perm, DevBuf &tmp, DevBuf &scan_tmp, const int64_t **n_heavy_dev,
+                           const int64_t **cls_pos /* or NULL: the scan itself, on the device -- class k is perm[cls_pos[k * n] .. cls_pos[(k + 1) * n]) */) {
     if (n <= 0) return BM2_OK;
     const size_t m = (size_t)BM2_WORK_CLASSES * (size_t)n;
     int rc = bm2_reserve(tmp, (m + 1) * 4 + (m + 2) * 8 + 64);
@@ -181,6 +182,7 @@ int bm2_partition_by_class(bm2_ctx *c, int n, const int32_t *key, int thr, int32
     int32_t *flag = (int32_t *)tmp.p;
     int64_t *pos = (int64_t *)((char *)tmp.p + (((m + 1) * 4 + 15) & ~(size_t)15));
     if (n_heavy_dev) *n_heavy_dev = pos + n;                   // where class 1 starts = how many heavy reads there are
+    if (cls_pos) *cls_pos = pos;                               // (pos[7 * n] = n: the scan's total closes the last class)
     hipLaunchKernelGGL(k_class_flag, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, key, thr, flag);
     if ((rc = bm2_scan_i32(c, flag, (int64_t)m, pos, scan_tmp))) return rc;
     hipLaunchKernelGGL(k_class_scatter, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, key, thr, pos, perm);

@@ -35,6 +35,14 @@ GRID = [   # (name, candidates): a candidate is a dict of knobs set together; th
      [{}] + [c for wpe in (3, 4) for wcu in (16, 24)
              for c in [dict(BM2_HEAVY_SA=t, BM2_CHAIN_HEAVY_WPE=wpe, BM2_CHAIN_WAVES_PER_CU=wcu) for t in (32, 40, 48, 56, 64, 72, 80)] +
                       [{}, {"BM2_CHAIN_LDS_COMPACT": 0}, {"BM2_CHAIN_LDS_COMPACT": 0, "BM2_HEAVY_SA": 80}]]),
+    ("chain group: lanes per light read (k_chain_group) x its lower bound x the threshold to the tiers, then wavefronts per CU and class; the default measured between",
+     [{}] + [c for g in (2, 4, 8) for mn in (0, 4, 8)
+             for c in [dict(BM2_CHAIN_GROUP=g, BM2_CHAIN_GROUP_MIN=mn, BM2_HEAVY_SA=t) for t in (40, 48, 56, 64, 72, 80)] + [{}]] +
+            [dict(BM2_CHAIN_GROUP=g, BM2_CHAIN_GROUP_MIN=mn, BM2_CHAIN_GROUP_WAVES_PER_CU=w) for g in (2, 4, 8) for mn in (4, 8, 16) for w in (4, 16)] +
+            [dict(BM2_HEAVY_SA=t) for t in (40, 48, 64, 72, 80)] + [{}]),
+    ("chain group, fine: only the seed-richer light classes to the lane groups (the coarse grid's best corner), the default measured between",
+     [{}] + [c for g in (4, 8) for w in (8, 16, 32)
+             for c in [dict(BM2_CHAIN_GROUP=g, BM2_CHAIN_GROUP_MIN=mn, BM2_CHAIN_GROUP_WAVES_PER_CU=w, BM2_HEAVY_SA=t) for mn in (12, 16, 24, 32) for t in (48, 56, 64, 72)] + [{}]]),
     ("chain clock", [{}, {"BM2_CHAIN_CLOCK": 1}]),
     ("chain staging", [{}, {"BM2_CHAIN_STAGE": 1}]),
     ("chain heavy threshold", [{}, {"BM2_HEAVY_SA": 100}, {"BM2_HEAVY_SA": 72}, {"BM2_HEAVY_SA": 64}]),

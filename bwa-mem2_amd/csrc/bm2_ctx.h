@@ -112,6 +112,12 @@ int  bm2_check(hipError_t e, const char *what);            // -> BM2_OK or BM2_E
 void bm2_set_error(const char *fmt, ...);
 int  bm2_reserve(DevBuf &b, size_t bytes);                  // grow-only device allocation
 void bm2_release(DevBuf &b);
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }      // the size of one array of a workspace carved into several
+// the context holds an index with its contig table, which the paired tail's rescue, plan and model kernels read
+inline bool bm2_ann_ready(const bm2_ctx *c, const char *who) {
+    if (!c || !c->has_index || !c->ix.ann_offset || !c->ix.ann_len) { bm2_set_error("%s: the context holds no index", who); return false; }
+    return true;
+}
 // Large copies between PAGEABLE host memory (the caller's arrays) and the device, staged through the context's pinned buffers in
 // 16 MB pieces: the DMA of one piece overlaps the host memcpy of the next (a plain hipMemcpy of pageable memory runs at a few GB/s).
 // Both return after the data has arrived.

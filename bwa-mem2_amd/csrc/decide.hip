@@ -31,7 +31,6 @@
 #include <string.h>
 #include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -467,7 +466,6 @@ __global__ __launch_bounds__(256) void k_decide_permute(const bm2_alnreg_t *__re
 
 namespace {
 std::atomic<long long> g_dc_pairs{0}, g_dc_hits{0}, g_dc_heavy{0};
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // (int)(4.343 * log(n + 1) + .499) with the host's log: the smallest n >= 1 of every step (the function does not descend)
 void step_thresholds(std::vector<int64_t> &thr) {
@@ -700,27 +698,12 @@ int bm2h_dev_decide_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so,
     int rc = bm2h_check_hit_off("BM2_SAM_F_DEVICE_DECIDE", n_pairs, hit_off);
     if (rc) return rc;
     g_dc_pairs = 0; g_dc_hits = 0; g_dc_heavy = 0;
-    const int64_t part_min = bm2_knob("BM2_DECIDE_PART", 65536);         // pairs that are worth a context of their own (launch policy)
-    int G = (int)(n_pairs / (part_min > 0 ? part_min : 1) + 1 < m->n ? n_pairs / (part_min > 0 ? part_min : 1) + 1 : m->n);
-    if (G < 1) G = 1;
+    const int G = bm2_parts(n_pairs, bm2_knob("BM2_DECIDE_PART", 65536), m->n);      // knob: pairs that are worth a context of their own (launch policy)
     if (G == 1) return decide_run(m->ctx[0], "BM2_SAM_F_DEVICE_DECIDE", opt, so, n_pairs, hits, hit_off, first_pair, pes, plans);
-    std::vector<int> rcs((size_t)G, 0);
-    std::vector<std::string> msgs((size_t)G);
-    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-    auto one = [&](int g) {
-        bm2_host_thread_budget() = budget;
-        const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
-        rcs[(size_t)g] = decide_run(m->ctx[g], "BM2_SAM_F_DEVICE_DECIDE", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, first_pair + lo, pes, plans + lo);
-        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-    };
-    const int mine = bm2_host_thread_budget();
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-    one(0);
-    for (auto &t : th) t.join();
-    bm2_host_thread_budget() = mine;
-    for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("%s", msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
-    return BM2_OK;
+    return bm2_run_parts(G, bm2_part_budget(G), nullptr, [&](int g) {
+        const int64_t lo = bm2_part_lo(n_pairs, g, G), hi = bm2_part_lo(n_pairs, g + 1, G);
+        return decide_run(m->ctx[g], "BM2_SAM_F_DEVICE_DECIDE", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, first_pair + lo, pes, plans + lo);
+    });
 }
 
-bm2h_decide_scope::bm2h_decide_scope(bm2_ctx *const *ctx, int n) : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n }, hook(bm2h_dev_decide_batch, &tc) {}
+bm2h_decide_scope::bm2h_decide_scope(bm2_ctx *const *ctx, int n) : bm2h_ctx_scope(ctx, n), hook(bm2h_dev_decide_batch, &tc) {}

@@ -1,4 +1,5 @@
-// host_pool.h -- the host side's worker threads (sam_tail.cpp, fastq_io.cpp): bm2_run_threads(n, f) runs n copies of f.
+// host_pool.h -- the host side's worker threads (sam_tail.cpp, fastq_io.cpp): bm2_run_threads(n, f) runs n copies of f;
+// bm2_run_parts(G, budget, label, f) runs the G parts of a batch cut over several contexts (the device hooks, the sharded hot path).
 #pragma once
 #include <limits.h>
 #include <linux/futex.h>
@@ -158,6 +159,44 @@ inline int bm2_host_threads() {
     const int b = bm2_host_thread_budget();
     if (b > 0) return b;
     return bm2_effective_cpus();
+}
+
+// ---- a batch over several contexts: G contiguous parts, one host thread (and one context) per part.
+// The parts n items are cut into: one per part_min items (n == part_min already makes two), at most n_ctx, at least 1; part g = [lo(g), lo(g + 1)).
+inline int bm2_parts(int64_t n, int64_t part_min, int n_ctx) {
+    const int64_t p = n / (part_min > 0 ? part_min : 1) + 1;
+    const int G = (int)(p < n_ctx ? p : n_ctx);
+    return G < 1 ? 1 : G;
+}
+inline int64_t bm2_part_lo(int64_t n, int g, int G) { return n * g / G; }
+// The budget of a part when the caller's host threads are shared out among G parts (a fresh thread would size its host loops to the whole machine).
+inline int bm2_part_budget(int G) { const int b = bm2_host_threads() / (G > 0 ? G : 1); return b > 0 ? b : 1; }
+void bm2_set_error(const char *fmt, ...);
+extern "C" const char *bm2_last_error(void);
+// f(g) -> BM2_* code for g = 0 .. G-1: part 0 on the calling thread, the others on fresh threads, all of them run to the end and joined.
+// budget > 0: every part runs with that host-thread budget, the caller's own is back when this returns; 0: no budget is touched.
+// The failing part with the lowest g wins: its code is returned, its message becomes the caller's ("<label> <g>: " in front unless label is NULL).
+template <class F> int bm2_run_parts(int G, int budget, const char *label, F f) {
+    if (G < 1) G = 1;
+    std::vector<int> rcs((size_t)G, 0);
+    std::vector<std::string> msgs((size_t)G);
+    auto one = [&](int g) {
+        if (budget > 0) bm2_host_thread_budget() = budget;
+        rcs[(size_t)g] = f(g);
+        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
+    };
+    const int mine = bm2_host_thread_budget();
+    std::vector<std::thread> th;
+    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
+    one(0);
+    for (auto &t : th) t.join();
+    bm2_host_thread_budget() = mine;
+    for (int g = 0; g < G; ++g) {
+        if (!rcs[(size_t)g]) continue;
+        if (label) bm2_set_error("%s %d: %s", label, g, msgs[(size_t)g].c_str()); else bm2_set_error("%s", msgs[(size_t)g].c_str());
+        return rcs[(size_t)g];
+    }
+    return 0;
 }
 
 inline void bm2_run_threads(int n_threads, std::function<void()> f) {

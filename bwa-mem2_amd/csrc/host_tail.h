@@ -39,10 +39,14 @@ struct bm2h_text_hook {             // scoped: the hook of the calling thread fo
 // no context believing that it still holds the reads of an earlier call.
 struct bm2_ctx;
 struct bm2h_text_ctxs { bm2_ctx *const *ctx; int n; };
+struct bm2h_ctx_scope {             // what every scope below holds: the contexts its hook works on (a lone one is kept here, not with the caller)
+    bm2_ctx *one; bm2h_text_ctxs tc;
+    bm2h_ctx_scope(bm2_ctx *const *ctx, int n) : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n } {}
+};
 int bm2h_dev_text_batch(void *user, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt, int64_t n_rec, const bm2_samrec_t *recs,
                         const uint32_t *cigar, int64_t n_cigar, const char *side, int64_t side_bytes, char *out, int64_t cap, int64_t *n_out);
-struct bm2h_text_scope {
-    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_text_hook hook;
+struct bm2h_text_scope : bm2h_ctx_scope {
+    bm2h_text_hook hook;
     bm2h_text_scope(bm2_ctx *const *ctx, int n);
     ~bm2h_text_scope();
 };
@@ -52,6 +56,12 @@ struct bm2h_text_scope {
 typedef int (*bm2h_decide_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
                                     const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
 int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off);       // non-negative, non-decreasing, every list below 2^30 hits
+// the n_lists + 1 offsets counted from the first list's (what a batch that starts anywhere in hit_off uploads)
+inline std::vector<int64_t> bm2h_hit_off_from0(const int64_t *hit_off, int64_t n_lists) {
+    std::vector<int64_t> hoff((size_t)n_lists + 1);
+    for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hit_off[0];
+    return hoff;
+}
 struct bm2h_decide_hook {
     bm2h_decide_hook(bm2h_decide_batch_fn fn, void *user);
     ~bm2h_decide_hook();
@@ -60,8 +70,8 @@ struct bm2h_decide_hook {
 // and the scope the _dev entry points of the paired tail open around their bm2h_sam_pe call.
 int bm2h_dev_decide_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, bm2_alnreg_t *hits,
                           const int64_t *hit_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans);
-struct bm2h_decide_scope {
-    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_decide_hook hook;
+struct bm2h_decide_scope : bm2h_ctx_scope {
+    bm2h_decide_hook hook;
     bm2h_decide_scope(bm2_ctx *const *ctx, int n);
 };
 // The rescue results of one chunk applied to its lists (bm2_pe_rescue_apply_dev's arguments after the context, with the results of the
@@ -92,8 +102,8 @@ int bm2h_dev_rescue_apply_batch(void *user, const bm2_opt *opt, const bm2_sam_op
 int bm2h_decide_resident(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *d_hits,
                          const int64_t *d_off, const int64_t *h_off, int64_t first_pair, const bm2_pestat pes[4], bm2_pairplan_t *plans, bm2_alnreg_t *out);
 void bm2h_decide_stats_reset();
-struct bm2h_rescue_scope {
-    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_rescue_hook hook;
+struct bm2h_rescue_scope : bm2h_ctx_scope {
+    bm2h_rescue_hook hook;
     bm2h_rescue_scope(bm2_ctx *const *ctx, int n);
 };
 // The plan of one chunk's mate rescue (bm2_pe_rescue_plan_dev's arguments after the context; the tasks go to what room(arg, n) answers
@@ -123,8 +133,8 @@ int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, i
 int bm2h_dev_rescue_batch_resident(void *user, int32_t n, const bm2_rescue_task_t *tasks, const bm2_reads *reads, const int64_t *q_off, const int32_t *q_len,
                                    const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, bm2_ksw_result *out);
 int bm2h_plan_queries_resident(bm2_ctx *c, const bm2_reads *reads, int64_t n, const bm2_rescue_task_t *tasks, const int64_t *q_off, uint8_t *d_out);
-struct bm2h_plan_scope {
-    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_plan_hook hook;
+struct bm2h_plan_scope : bm2h_ctx_scope {
+    bm2h_plan_hook hook;
     bm2h_plan_scope(bm2_ctx *const *ctx, int n);
 };
 // The contiguous parts a chunk's pairs are cut into by the hooks that read its hit lists (the plan's and the model's: the same parts, so
@@ -151,8 +161,8 @@ uint64_t bm2h_tail_epoch();
 // histograms summed on the host) and its scope, which also forgets what the contexts hold in b_pl_in when the call ends.
 int bm2h_dev_pestat_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
                           bm2_pestat pes[4]);
-struct bm2h_pestat_scope {
-    bm2_ctx *one; bm2h_text_ctxs tc; bm2h_pestat_hook hook;
+struct bm2h_pestat_scope : bm2h_ctx_scope {
+    bm2h_pestat_hook hook;
     bm2h_pestat_scope(bm2_ctx *const *ctx, int n);
     ~bm2h_pestat_scope();
 };

@@ -12,7 +12,6 @@
 #include <numeric>
 #include <string>
 #include <string.h>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -190,11 +189,9 @@ static int dev_rescue_batch(void *user, int32_t n, const uint8_t *qbuf, int64_t 
 int bm2h_dev_rescue_batch_resident(void *user, int32_t n, const bm2_rescue_task_t *tasks, const bm2_reads *reads, const int64_t *q_off, const int32_t *q_len,
                                    const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, bm2_ksw_result *out) {
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
-    const int64_t part_min = bm2_knob("BM2_KSW_PART", 8192);             // tasks that are worth a context of their own (launch policy)
-    int G = (int)((int64_t)n / (part_min > 0 ? part_min : 1) + 1 < m->n ? (int64_t)n / (part_min > 0 ? part_min : 1) + 1 : m->n);
-    if (G < 1) G = 1;
+    const int G = bm2_parts(n, bm2_knob("BM2_KSW_PART", 8192), m->n);       // knob: tasks that are worth a context of their own (launch policy)
     auto part = [&](int g) {
-        const int64_t lo = (int64_t)n * g / G, hi = (int64_t)n * (g + 1) / G;
+        const int64_t lo = bm2_part_lo(n, g, G), hi = bm2_part_lo(n, g + 1, G);
         bm2_ctx *c = m->ctx[g];
         const RefPtr ref = c->ix.ref(0);
         const KswMade made = { reads, tasks + lo };
@@ -202,22 +199,7 @@ int bm2h_dev_rescue_batch_resident(void *user, int32_t n, const bm2_rescue_task_
                              opt->o_ins, opt->e_ins, out + lo, &made);
     };
     if (G == 1) return part(0);
-    std::vector<int> rcs((size_t)G, 0);
-    std::vector<std::string> msgs((size_t)G);
-    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-    auto one = [&](int g) {
-        bm2_host_thread_budget() = budget;
-        rcs[(size_t)g] = part(g);
-        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-    };
-    const int mine = bm2_host_thread_budget();
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-    one(0);
-    for (auto &t : th) t.join();
-    bm2_host_thread_budget() = mine;
-    for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("context %d: %s", g, msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
-    return BM2_OK;
+    return bm2_run_parts(G, bm2_part_budget(G), "context", part);
 }
 
 extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,
@@ -238,45 +220,23 @@ extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
 // context per part, and the results are put back in task order -- the text cannot depend on the number of contexts.  (bwamem.cpp:1366-1381 runs
 // them inside worker_sam on every host thread; with G GPUs the hot path of a chunk shrinks G-fold and the tail's batches have to follow.)
 namespace {
-struct MultiCtx { bm2_ctx *const *ctx; int n; };
-template <class F> int run_parts(int parts, int budget, F f) {          // f(part) on a thread of its own; first error wins
-    std::vector<int> rcs((size_t)parts, 0);
-    std::vector<std::string> msgs((size_t)parts);
-    auto one = [&](int g) {
-        bm2_host_thread_budget() = budget;                                  // (a fresh thread would size its host loops to the whole machine)
-        rcs[(size_t)g] = f(g);
-        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-    };
-    std::vector<std::thread> th;
-    for (int g = 1; g < parts; g++) th.emplace_back(one, g);
-    const int mine = bm2_host_thread_budget();
-    one(0);
-    bm2_host_thread_budget() = mine;
-    for (auto &t : th) t.join();
-    for (int g = 0; g < parts; g++) if (rcs[(size_t)g]) { bm2_set_error("context %d: %s", g, msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
-    return BM2_OK;
-}
-int parts_of(const MultiCtx *m, int64_t n, int64_t grain) { int64_t p = n / grain + 1; return (int)(p < m->n ? p : m->n); }
-
 int multi_rescue_batch(void *user, int32_t n, const uint8_t *qbuf, int64_t qbuf_bytes, const int64_t *q_off, const int32_t *q_len,
                        const int64_t *t_pos, const int32_t *t_len, const int32_t *xtra, const bm2_opt *opt, const uint8_t *unused, bm2_ksw_result *out) {
-    const MultiCtx *m = (const MultiCtx *)user;
-    const int G = parts_of(m, n, 8192);
+    const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
+    const int G = bm2_parts(n, 8192, m->n);
     if (G <= 1) return dev_rescue_batch(m->ctx[0], n, qbuf, qbuf_bytes, q_off, q_len, t_pos, t_len, xtra, opt, unused, out);
-    const int budget = bm2_host_threads() / G > 0 ? bm2_host_threads() / G : 1;
-    return run_parts(G, budget, [&](int g) {
-        const int64_t lo = (int64_t)n * g / G, hi = (int64_t)n * (g + 1) / G;
+    return bm2_run_parts(G, bm2_part_budget(G), "context", [&](int g) {
+        const int64_t lo = bm2_part_lo(n, g, G), hi = bm2_part_lo(n, g + 1, G);
         return dev_rescue_batch(m->ctx[g], (int32_t)(hi - lo), qbuf, qbuf_bytes, q_off + lo, q_len + lo, t_pos + lo, t_len + lo, xtra + lo, opt, unused, out + lo);
     });
 }
 int multi_cigar_batch(void *user, const bm2_opt *opt, const bm2_reads *reads, int64_t enc_bytes, int32_t n, const bm2h_cg_hit *hits, bm2h_cg_out *out) {
-    const MultiCtx *m = (const MultiCtx *)user;
-    const int G = parts_of(m, n, 16384);
+    const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
+    const int G = bm2_parts(n, 16384, m->n);
     if (G <= 1) return bm2_dev_cigar_batch(m->ctx[0], opt, reads, enc_bytes, n, hits, out);
     std::vector<bm2h_cg_out> part((size_t)G);
-    const int budget = bm2_host_threads() / G > 0 ? bm2_host_threads() / G : 1;
-    int rc = run_parts(G, budget, [&](int g) {
-        const int64_t lo = (int64_t)n * g / G, hi = (int64_t)n * (g + 1) / G;
+    int rc = bm2_run_parts(G, bm2_part_budget(G), "context", [&](int g) {
+        const int64_t lo = bm2_part_lo(n, g, G), hi = bm2_part_lo(n, g + 1, G);
         return bm2_dev_cigar_batch(m->ctx[g], opt, reads, enc_bytes, (int32_t)(hi - lo), hits + lo, &part[(size_t)g]);
     });
     if (rc) return rc;
@@ -309,7 +269,7 @@ extern "C" int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
                                     const bm2_read_text *txt, const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed,
                                     const bm2_pestat *pes_in, bm2_pestat *pes_out, char *out, int64_t cap, int64_t *n_out) {
     if (!all_hold_index(ctxs, n_ctx)) { bm2_set_error("bm2_sam_pe_dev_multi: every context must hold the index"); return BM2_EINVAL; }
-    MultiCtx m = { ctxs, n_ctx };
+    bm2h_text_ctxs m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
     bm2h_decide_scope decide(ctxs, n_ctx);
     bm2h_rescue_scope rescue(ctxs, n_ctx);
@@ -321,7 +281,7 @@ extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
                                     const bm2_read_text *txt, bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, char *out,
                                     int64_t cap, int64_t *n_out) {
     if (!all_hold_index(ctxs, n_ctx)) { bm2_set_error("bm2_sam_se_dev_multi: every context must hold the index"); return BM2_EINVAL; }
-    MultiCtx m = { ctxs, n_ctx };
+    bm2h_text_ctxs m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, multi_cigar_batch, &m);
 }

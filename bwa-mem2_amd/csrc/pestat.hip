@@ -13,7 +13,6 @@
 #include <stdint.h>
 #include <string.h>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -67,11 +66,6 @@ __global__ __launch_bounds__(256) void k_pestat_reduce(uint32_t *__restrict__ hi
 }
 
 namespace {
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool pestat_ready(const bm2_ctx *c, const char *who) {
-    if (!c || !c->has_index || !c->ix.ann_offset || !c->ix.ann_len) { bm2_set_error("%s: the context holds no index", who); return false; }
-    return true;
-}
 // Copies of the histogram for `blocks` blocks adding into 4 * bins counts: the knob, at most one per block, and no more than fit 32 MB
 // -- 16 at the default max_ins (160 KB a copy), 1 from max_ins = 2^20 on (16 MB a copy; 268 MB at the 2^24 limit).
 int pestat_copies(int64_t bins, int64_t blocks) {
@@ -111,8 +105,7 @@ static int pestat_run(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int
     P.l_pac = c->ix.l_pac; P.bins = bins; P.n_pairs = n_pairs; P.max_ins = so->max_ins; P.min_seed_len = opt->min_seed_len; P.a = opt->a;
     P.copies = copies; P.mask_level = opt->mask_level;
     uint32_t *d_hist = (uint32_t *)c->b_pl_work.p;
-    std::vector<int64_t> hoff((size_t)n_lists + 1);
-    for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hbase;
+    const std::vector<int64_t> hoff = bm2h_hit_off_from0(hit_off, n_lists);
     if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits + hbase, (size_t)n_hits * sizeof(bm2_alnreg_t)))) return rc;
     if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
     *hit_bytes_up = (int64_t)((size_t)n_hits * sizeof(bm2_alnreg_t));
@@ -140,7 +133,7 @@ static long long pestat_counted(const std::vector<uint32_t> &h) { long long n = 
 extern "C" int bm2_pe_stat_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
                                const int64_t *hit_off, bm2_pestat pes[4], uint32_t *hist, int64_t hist_cap) {
     if (!c || !opt || !so || n_pairs < 0 || !hit_off || !pes || hist_cap < 0) { bm2_set_error("bm2_pe_stat_dev: bad argument"); return BM2_EINVAL; }
-    if (!pestat_ready(c, "bm2_pe_stat_dev")) return BM2_EINVAL;
+    if (!bm2_ann_ready(c, "bm2_pe_stat_dev")) return BM2_EINVAL;
     int rc = bm2h_check_hit_off("bm2_pe_stat_dev", n_pairs, hit_off);
     if (rc) return rc;
     if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("bm2_pe_stat_dev: bad argument"); return BM2_EINVAL; }
@@ -163,7 +156,7 @@ extern "C" int bm2_pe_stat_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt
 int bm2h_dev_pestat_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
                           bm2_pestat pes[4]) {
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
-    for (int g = 0; g < m->n; ++g) if (!pestat_ready(m->ctx[g], "BM2_SAM_F_DEVICE_PESTAT")) return BM2_EINVAL;
+    for (int g = 0; g < m->n; ++g) if (!bm2_ann_ready(m->ctx[g], "BM2_SAM_F_DEVICE_PESTAT")) return BM2_EINVAL;
     bm2h_pestat_stats_set(0, 0, 0);
     int rc = bm2h_check_hit_off("BM2_SAM_F_DEVICE_PESTAT", n_pairs, hit_off);
     if (rc) return rc;
@@ -177,25 +170,14 @@ int bm2h_dev_pestat_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so,
     if (top > 0 && G == 1) {
         if ((rc = pestat_run(m->ctx[0], opt, so, n_pairs, hits, hit_off, h.data(), epoch, &up))) return rc;
     } else if (top > 0) {
-        std::vector<int> rcs((size_t)G, 0);
-        std::vector<std::string> msgs((size_t)G);
         std::vector<int64_t> ups((size_t)G, 0);
         std::vector<std::vector<uint32_t>> part((size_t)G);
-        const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-        auto one = [&](int g) {
-            bm2_host_thread_budget() = budget;
-            const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
+        rc = bm2_run_parts(G, bm2_part_budget(G), nullptr, [&](int g) {
+            const int64_t lo = bm2_part_lo(n_pairs, g, G), hi = bm2_part_lo(n_pairs, g + 1, G);
             part[(size_t)g].resize(n_cnt);
-            rcs[(size_t)g] = pestat_run(m->ctx[g], opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, part[(size_t)g].data(), epoch, &ups[(size_t)g]);
-            if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-        };
-        const int mine = bm2_host_thread_budget();
-        std::vector<std::thread> th;
-        for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-        one(0);
-        for (auto &t : th) t.join();
-        bm2_host_thread_budget() = mine;
-        for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("%s", msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
+            return pestat_run(m->ctx[g], opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, part[(size_t)g].data(), epoch, &ups[(size_t)g]);
+        });
+        if (rc) return rc;
         for (int g = 0; g < G; ++g) {
             const uint32_t *o = part[(size_t)g].data();
             for (size_t v = 0; v < n_cnt; ++v) h[v] += o[v];
@@ -208,5 +190,5 @@ int bm2h_dev_pestat_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so,
 }
 
 bm2h_pestat_scope::bm2h_pestat_scope(bm2_ctx *const *ctx, int n)
-    : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n }, hook(bm2h_dev_pestat_batch, &tc) {}
+    : bm2h_ctx_scope(ctx, n), hook(bm2h_dev_pestat_batch, &tc) {}
 bm2h_pestat_scope::~bm2h_pestat_scope() { for (int g = 0; g < tc.n; ++g) if (tc.ctx[g]) tc.ctx[g]->pl_res.epoch = 0; }

@@ -530,8 +530,7 @@ static int batch_kernel_ms_one(bm2_ctx *c, float *ms, int32_t cap, int32_t *n_ou
 // the path, bwamem.cpp:834, is per 512-read block, so parts are independent).  Every part has its own streams and
 // workspace and is driven by its own host thread, so the latency-bound stages of one part (chaining, the tails of the
 // extension launches, the host round trips for buffer sizes) overlap the bandwidth- and ALU-bound kernels of the others.
-#include <thread>
-#include <string>
+#include "host_pool.h"
 
 static bm2_ctx *part_ctx(bm2_ctx *c, int i) { return i == 0 ? c : c->subs[i - 1]; }
 
@@ -572,18 +571,11 @@ extern "C" int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads) {
 extern "C" int bm2_batch_run(bm2_ctx *c, const bm2_opt *opt) {
     if (!c) return BM2_EINVAL;
     if (c->n_parts <= 1) return batch_run_one(c, opt);
-    std::vector<int> rcs(c->n_parts, 0);
-    std::vector<std::string> msgs(c->n_parts);
-    std::vector<std::thread> th;
     // the parts on their own host threads, streams and workspaces; staggered by the gate (BM2_SUB_STAGGER=0: all at once, the round-2 form,
     // in which the parts sat in the same stage at the same time and gained nothing from each other)
     StageGate *gate = bm2_knob("BM2_SUB_STAGGER", 0) ? &c->gate : nullptr;   // (measured: 100.5 ms staggered, 87.9 ms together, 81.3 ms as ONE part -- profiles/r03k_staggered_parts.json)
     c->gate.reset();
-    for (int i = 0; i < c->n_parts; i++)
-        th.emplace_back([&, i]() { rcs[i] = batch_run_one(part_ctx(c, i), opt, gate, i); if (rcs[i]) msgs[i] = bm2_last_error(); });
-    for (auto &t : th) t.join();
-    for (int i = 0; i < c->n_parts; i++) if (rcs[i]) { bm2_set_error("part %d: %s", i, msgs[i].c_str()); return rcs[i]; }
-    return BM2_OK;
+    return bm2_run_parts(c->n_parts, 0, "part", [&](int i) { return batch_run_one(part_ctx(c, i), opt, gate, i); });
 }
 
 extern "C" int bm2_batch_parts(const bm2_ctx *c) { return !c ? 0 : c->n_parts < 1 ? 1 : c->n_parts; }
@@ -739,10 +731,8 @@ extern "C" int bm2_chunk_hits_sharded(bm2_ctx *const *ctxs, int n_ctx, const bm2
     std::vector<int> first((size_t)n_ctx + 1);
     for (int i = 0; i <= n_ctx; i++) { const int64_t b = (int64_t)blocks * i / n_ctx * BM2_BLOCK_READS; first[(size_t)i] = (int)(b < n ? b : n); }
     first[(size_t)n_ctx] = n;
-    std::vector<int> rcs((size_t)n_ctx, 0);
-    std::vector<std::string> msgs((size_t)n_ctx);
     std::vector<std::vector<int64_t>> offs((size_t)n_ctx);
-    auto device_part = [&](int i) {
+    int rc = bm2_run_parts(n_ctx, 0, "context", [&](int i) {
         const int lo = first[(size_t)i], hi = first[(size_t)i + 1];
         bm2_reads r; r.n_reads = hi - lo; r.enc = reads->enc; r.off = reads->off + lo; r.len = reads->len + lo;
         std::vector<int64_t> off2;
@@ -756,16 +746,9 @@ extern "C" int bm2_chunk_hits_sharded(bm2_ctx *const *ctxs, int n_ctx, const bm2
         int rc = bm2_batch_upload(ctxs[i], &r);
         if (!rc) rc = bm2_batch_run(ctxs[i], opt);
         if (!rc) rc = bm2_batch_finish(ctxs[i], opt);
-        rcs[(size_t)i] = rc;
-        if (rc) msgs[(size_t)i] = bm2_last_error();
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 1; i < n_ctx; i++) th.emplace_back(device_part, i);
-        device_part(0);
-        for (auto &t : th) t.join();
-    }
-    for (int i = 0; i < n_ctx; i++) if (rcs[(size_t)i]) { bm2_set_error("context %d: %s", i, msgs[(size_t)i].c_str()); return rcs[(size_t)i]; }
+        return rc;
+    });
+    if (rc) return rc;
     // gather in read order
     int64_t tot = 0;
     std::vector<int64_t> cnt((size_t)n_ctx);
@@ -781,22 +764,16 @@ extern "C" int bm2_chunk_hits_sharded(bm2_ctx *const *ctxs, int n_ctx, const bm2
     // parts' hit counts; G copies over G links instead of one after the other)
     std::vector<int64_t> base((size_t)n_ctx + 1, 0);
     for (int i = 0; i < n_ctx; i++) base[(size_t)i + 1] = base[(size_t)i] + cnt[(size_t)i];
-    auto download_part = [&](int i) {
+    rc = bm2_run_parts(n_ctx, 0, "context", [&](int i) {
         const int lo = first[(size_t)i], hi = first[(size_t)i + 1];
         int64_t n1 = 0;
         offs[(size_t)i].assign((size_t)(hi - lo) + 1, 0);
         const int rc = bm2_batch_download_alnregs(ctxs[i], out ? out + base[(size_t)i] : nullptr, cap - base[(size_t)i], offs[(size_t)i].data(), &n1);
-        rcs[(size_t)i] = rc;
-        if (rc) { msgs[(size_t)i] = bm2_last_error(); return; }
+        if (rc) return rc;
         for (int k = 0; k <= hi - lo; k++) aln_off[lo + k] = offs[(size_t)i][(size_t)k] + base[(size_t)i];
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 1; i < n_ctx; i++) th.emplace_back(download_part, i);
-        download_part(0);
-        for (auto &t : th) t.join();
-    }
-    for (int i = 0; i < n_ctx; i++) if (rcs[(size_t)i]) { bm2_set_error("context %d: %s", i, msgs[(size_t)i].c_str()); return rcs[(size_t)i]; }
+        return BM2_OK;
+    });
+    if (rc) return rc;
     aln_off[n] = tot;
     return BM2_OK;
 }

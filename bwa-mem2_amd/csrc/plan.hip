@@ -17,7 +17,6 @@
 #include <string.h>
 #include <functional>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -119,11 +118,6 @@ __global__ __launch_bounds__(256) void k_plan_queries(const uint8_t *__restrict_
 #define PL_ENC_BACK 8
 
 namespace {
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool plan_ready(const bm2_ctx *c, const char *who) {
-    if (!c || !c->has_index || !c->ix.ann_offset || !c->ix.ann_len) { bm2_set_error("%s: the context holds no index", who); return false; }
-    return true;
-}
 typedef std::function<bm2_rescue_task_t *(int64_t)> PlRoom;      // room for n tasks (NULL: none to be had)
 }  // namespace
 
@@ -163,8 +157,7 @@ static int plan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_s
     P.n_pairs = n_pairs; P.min_seed_len = opt->min_seed_len; P.pen_unpaired = so->pen_unpaired; P.max_matesw = so->max_matesw; P.pair_base = pair_base;
     for (int k = 0; k < 4; ++k) { P.low[k] = pes[k].low; P.high[k] = pes[k].high; P.failed[k] = pes[k].failed; }
     if (!resident) {
-        std::vector<int64_t> hoff((size_t)n_lists + 1);
-        for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hbase;
+        const std::vector<int64_t> hoff = bm2h_hit_off_from0(hit_off, n_lists);
         if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits + hbase, (size_t)n_hits * sizeof(bm2_alnreg_t)))) return rc;
         if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
     } else bm2h_pestat_stats_shared((long long)((size_t)n_hits * sizeof(bm2_alnreg_t)), true);
@@ -201,7 +194,7 @@ extern "C" int bm2_pe_rescue_plan_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_
     if (!c || !opt || !so || n_pairs < 0 || !hit_off || !pes || !task_off || !n_out || cap < 0 || (cap > 0 && !tasks) || (n_pairs > 0 && !read_len)) {
         bm2_set_error("bm2_pe_rescue_plan_dev: bad argument"); return BM2_EINVAL;
     }
-    if (!plan_ready(c, "bm2_pe_rescue_plan_dev")) return BM2_EINVAL;
+    if (!bm2_ann_ready(c, "bm2_pe_rescue_plan_dev")) return BM2_EINVAL;
     int rc = bm2h_check_hit_off("bm2_pe_rescue_plan_dev", n_pairs, hit_off);
     if (rc) return rc;
     if (hit_off[2 * (int64_t)n_pairs] > hit_off[0] && !hits) { bm2_set_error("bm2_pe_rescue_plan_dev: bad argument"); return BM2_EINVAL; }
@@ -266,19 +259,15 @@ extern "C" int bm2_pe_rescue_queries_dev(bm2_ctx *c, const bm2_reads *reads, int
     return bm2_copy_d2h(c, out, c->b_pl_out.p, (size_t)bytes);       // (waits for the kernel: same stream)
 }
 
-int bm2h_plan_parts(int64_t n_pairs, int n_ctx) {
-    const int64_t part_min = bm2_knob("BM2_PLAN_PART", 65536);           // pairs that are worth a context of their own (launch policy)
-    int G = (int)(n_pairs / (part_min > 0 ? part_min : 1) + 1 < n_ctx ? n_pairs / (part_min > 0 ? part_min : 1) + 1 : n_ctx);
-    return G < 1 ? 1 : G;
-}
+int bm2h_plan_parts(int64_t n_pairs, int n_ctx) { return bm2_parts(n_pairs, bm2_knob("BM2_PLAN_PART", 65536), n_ctx); }      // knob: pairs that are worth a context of their own (launch policy)
 
 // ---- the hook of the SAM tail (bm2h_plan_batch_fn; user = bm2h_text_ctxs): the chunk's pairs cut into contiguous parts, one context
-// and one host thread per part, as the other hooks do.  A pair's tasks depend on its own lists and the chunk's model only.
+// and one host thread per part (bm2_run_parts).  A pair's tasks depend on its own lists and the chunk's model only.
 int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
                         const int32_t *read_len, const bm2_pestat pes[4], bm2_rescue_task_t *(*room)(void *arg, int64_t n), void *arg,
                         int64_t *task_off, int64_t *n_out) {
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
-    for (int g = 0; g < m->n; ++g) if (!plan_ready(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN")) return BM2_EINVAL;
+    for (int g = 0; g < m->n; ++g) if (!bm2_ann_ready(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN")) return BM2_EINVAL;
     bm2h_plan_stats_set(0, 0, 0);
     bm2h_pestat_stats_shared(0, false);
     const uint64_t epoch = bm2h_tail_epoch();
@@ -289,27 +278,16 @@ int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, i
         if (!rc) bm2h_plan_stats_set(n_pairs, *n_out, 0);
         return rc;
     }
-    std::vector<int> rcs((size_t)G, 0);
-    std::vector<std::string> msgs((size_t)G);
     std::vector<int64_t> got((size_t)G, 0);
     std::vector<std::vector<bm2_rescue_task_t>> part((size_t)G);
     std::vector<std::vector<int64_t>> poff((size_t)G);
-    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-    auto one = [&](int g) {
-        bm2_host_thread_budget() = budget;
-        const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
+    const int rc = bm2_run_parts(G, bm2_part_budget(G), nullptr, [&](int g) {
+        const int64_t lo = bm2_part_lo(n_pairs, g, G), hi = bm2_part_lo(n_pairs, g + 1, G);
         poff[(size_t)g].resize((size_t)(hi - lo + 1));
-        rcs[(size_t)g] = plan_run(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, read_len + 2 * lo, pes, (int32_t)lo,
+        return plan_run(m->ctx[g], "BM2_SAM_F_DEVICE_PLAN", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, read_len + 2 * lo, pes, (int32_t)lo,
                                   [&, g](int64_t n) { part[(size_t)g].resize((size_t)n); return part[(size_t)g].data(); }, INT64_MAX, poff[(size_t)g].data(), &got[(size_t)g], epoch);
-        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-    };
-    const int mine = bm2_host_thread_budget();
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-    one(0);
-    for (auto &t : th) t.join();
-    bm2_host_thread_budget() = mine;
-    for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("%s", msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
+    });
+    if (rc) return rc;
     int64_t tot = 0;
     for (int g = 0; g < G; ++g) tot += got[(size_t)g];
     bm2_rescue_task_t *dst = tot > 0 ? room(arg, tot) : nullptr;
@@ -328,4 +306,4 @@ int bm2h_dev_plan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, i
 }
 
 bm2h_plan_scope::bm2h_plan_scope(bm2_ctx *const *ctx, int n)
-    : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n }, hook(bm2h_dev_plan_batch, bm2h_dev_rescue_batch_resident, &tc) {}
+    : bm2h_ctx_scope(ctx, n), hook(bm2h_dev_plan_batch, bm2h_dev_rescue_batch_resident, &tc) {}

@@ -22,7 +22,6 @@
 #include <string.h>
 #include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -210,14 +209,6 @@ __global__ __launch_bounds__(256) void k_rescue_gather(RsPrm P, const int64_t *_
 }
 static_assert(sizeof(bm2_alnreg_t) == 96 && offsetof(bm2_alnreg_t, pad) == 84, "k_rescue_gather moves a hit as six 16-byte words and knows where pad lies");
 
-namespace {
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool rescue_ready(const bm2_ctx *c, const char *who) {
-    if (!c || !c->has_index || !c->ix.ann_offset || !c->ix.ann_len) { bm2_set_error("%s: the context holds no index", who); return false; }
-    return true;
-}
-}  // namespace
-
 // The batch on one context.  Offsets may start anywhere (a part of a larger batch); out_off comes back from 0.  The caller has
 // checked offsets and tasks.  out_cap < what the lists need: BM2_ECAP with the need in *n_out and nothing written to `out`.
 int bm2h_rescue_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits,
@@ -231,8 +222,8 @@ int bm2h_rescue_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_s
     const int64_t n_lists = 2 * (int64_t)n_pairs, hbase = hit_off[0], n_hits = hit_off[n_lists] - hbase;
     const int64_t tbase = task_off[0], n_tasks = task_off[n_pairs] - tbase;
     if (n_hits + n_tasks > 0x7fffffff) { bm2_set_error("%s: more than 2^31 hits and tasks in one batch", who); return BM2_EINVAL; }
-    std::vector<int64_t> hoff((size_t)n_lists + 1), toff((size_t)n_pairs + 1);
-    for (int64_t i = 0; i <= n_lists; ++i) hoff[(size_t)i] = hit_off[i] - hbase;
+    const std::vector<int64_t> hoff = bm2h_hit_off_from0(hit_off, n_lists);
+    std::vector<int64_t> toff((size_t)n_pairs + 1);
     for (int64_t p = 0; p <= n_pairs; ++p) toff[(size_t)p] = task_off[p] - tbase;
     // the pairs with tasks, in classes of cost, each class in the pairs' own order
     int cnt[RS_CLASSES + 1] = { 0 };
@@ -325,7 +316,7 @@ extern "C" int bm2_pe_rescue_apply_dev(bm2_ctx *c, const bm2_opt *opt, const bm2
     if (!c || !opt || !so || n_pairs < 0 || !hit_off || !task_off || !pes || !n_out || !out_off || out_cap < 0 || (n_pairs > 0 && (!read_len || !redo))) {
         bm2_set_error("bm2_pe_rescue_apply_dev: bad argument"); return BM2_EINVAL;
     }
-    if (!rescue_ready(c, "bm2_pe_rescue_apply_dev")) return BM2_EINVAL;
+    if (!bm2_ann_ready(c, "bm2_pe_rescue_apply_dev")) return BM2_EINVAL;
     int rc = bm2h_check_rescue_tasks("bm2_pe_rescue_apply_dev", so, n_pairs, hits, hit_off, tasks, task_off);
     if (rc) return rc;
     if (out_cap > 0 && !out) { bm2_set_error("bm2_pe_rescue_apply_dev: bad argument"); return BM2_EINVAL; }
@@ -334,23 +325,19 @@ extern "C" int bm2_pe_rescue_apply_dev(bm2_ctx *c, const bm2_opt *opt, const bm2
 }
 
 // ---- the hook of the SAM tail (bm2h_rescue_batch_fn; user = bm2h_text_ctxs): the chunk's pairs cut into contiguous parts, one context
-// and one host thread per part, as the decide hook does.  A pair's lists depend on its own hits, tasks and the chunk's model only.
+// and one host thread per part (bm2_run_parts).  A pair's lists depend on its own hits, tasks and the chunk's model only.
 int bm2h_dev_rescue_apply_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_pairs, const bm2_alnreg_t *hits, const int64_t *hit_off,
                                 const int32_t *read_len, const bm2_pestat pes[4], const bm2_rescue_task_t *tasks, const bm2_ksw_result *res,
                                 const int64_t *task_off, bm2_alnreg_t *out, int64_t out_cap, int64_t *out_off, int32_t *redo, int64_t first_pair,
                                 bm2_pairplan_t *plans) {
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
-    for (int g = 0; g < m->n; ++g) if (!rescue_ready(m->ctx[g], "BM2_SAM_F_DEVICE_RESCUE")) return BM2_EINVAL;
+    for (int g = 0; g < m->n; ++g) if (!bm2_ann_ready(m->ctx[g], "BM2_SAM_F_DEVICE_RESCUE")) return BM2_EINVAL;
     bm2h_rescue_stats_reset();
     if (plans) bm2h_decide_stats_reset();
-    const int64_t part_min = bm2_knob("BM2_RESCUE_PART", 65536);         // pairs that are worth a context of their own (launch policy)
-    int G = (int)(n_pairs / (part_min > 0 ? part_min : 1) + 1 < m->n ? n_pairs / (part_min > 0 ? part_min : 1) + 1 : m->n);
-    if (G < 1) G = 1;
+    const int G = bm2_parts(n_pairs, bm2_knob("BM2_RESCUE_PART", 65536), m->n);      // knob: pairs that are worth a context of their own (launch policy)
     int64_t n_out = 0;
     if (G == 1) return bm2h_rescue_run(m->ctx[0], "BM2_SAM_F_DEVICE_RESCUE", opt, so, n_pairs, hits, hit_off, read_len, pes, tasks, res, task_off, 0, out, out_cap, out_off, redo, &n_out, first_pair, plans);
     // every part's output lies where its input hits and tasks would: room for whatever the part can make; then the parts are closed up
-    std::vector<int> rcs((size_t)G, 0);
-    std::vector<std::string> msgs((size_t)G);
     std::vector<int64_t> got((size_t)G, 0), at((size_t)G + 1, 0);
     std::vector<std::vector<int64_t>> poff((size_t)G);
     for (int g = 0; g < G; ++g) {
@@ -358,22 +345,13 @@ int bm2h_dev_rescue_apply_batch(void *user, const bm2_opt *opt, const bm2_sam_op
         at[(size_t)g + 1] = at[(size_t)g] + (hit_off[2 * hi] - hit_off[2 * lo]) + (task_off[hi] - task_off[lo]);
     }
     if (at[(size_t)G] > out_cap) { bm2_set_error("BM2_SAM_F_DEVICE_RESCUE: the output has room for %lld hits, the parts may need %lld", (long long)out_cap, (long long)at[(size_t)G]); return BM2_ECAP; }
-    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-    auto one = [&](int g) {
-        bm2_host_thread_budget() = budget;
-        const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
+    const int rc = bm2_run_parts(G, bm2_part_budget(G), nullptr, [&](int g) {
+        const int64_t lo = bm2_part_lo(n_pairs, g, G), hi = bm2_part_lo(n_pairs, g + 1, G);
         poff[(size_t)g].resize((size_t)(2 * (hi - lo) + 1));
-        rcs[(size_t)g] = bm2h_rescue_run(m->ctx[g], "BM2_SAM_F_DEVICE_RESCUE", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, read_len + 2 * lo, pes, tasks, res,
+        return bm2h_rescue_run(m->ctx[g], "BM2_SAM_F_DEVICE_RESCUE", opt, so, (int32_t)(hi - lo), hits, hit_off + 2 * lo, read_len + 2 * lo, pes, tasks, res,
                                          task_off + lo, 0, out + at[(size_t)g], at[(size_t)g + 1] - at[(size_t)g], poff[(size_t)g].data(), redo + lo, &got[(size_t)g], first_pair + lo, plans ? plans + lo : nullptr);
-        if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error();
-    };
-    const int mine = bm2_host_thread_budget();
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-    one(0);
-    for (auto &t : th) t.join();
-    bm2_host_thread_budget() = mine;
-    for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("%s", msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
+    });
+    if (rc) return rc;
     int64_t base = 0;
     for (int g = 0; g < G; ++g) {
         const int64_t lo = (int64_t)n_pairs * g / G, hi = (int64_t)n_pairs * (g + 1) / G;
@@ -385,4 +363,4 @@ int bm2h_dev_rescue_apply_batch(void *user, const bm2_opt *opt, const bm2_sam_op
     return BM2_OK;
 }
 
-bm2h_rescue_scope::bm2h_rescue_scope(bm2_ctx *const *ctx, int n) : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n }, hook(bm2h_dev_rescue_apply_batch, &tc) {}
+bm2h_rescue_scope::bm2h_rescue_scope(bm2_ctx *const *ctx, int n) : bm2h_ctx_scope(ctx, n), hook(bm2h_dev_rescue_apply_batch, &tc) {}

@@ -17,7 +17,6 @@
 #include <string.h>
 #include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/bm2.h"
 #include "bm2_ctx.h"
@@ -397,27 +396,11 @@ int bm2h_dev_text_batch(void *user, const bm2_sam_opt *so, const bm2_reads *read
     for (int g = 0; g < m->n; ++g) if (!text_ready(m->ctx[g], "BM2_SAM_F_DEVICE_TEXT")) return BM2_EINVAL;
     if (n_rec > 0x7fffffff) { bm2_set_error("BM2_SAM_F_DEVICE_TEXT: too many records in one chunk"); return BM2_EINVAL; }
     if (n_rec == 0) return BM2_OK;
-    const int64_t part_min = bm2_knob("BM2_TEXT_PART", 65536);          // records that are worth a context of their own (launch policy)
-    int G = (int)(n_rec / (part_min > 0 ? part_min : 1) + 1 < m->n ? n_rec / (part_min > 0 ? part_min : 1) + 1 : m->n);
-    if (G < 1) G = 1;
+    const int G = bm2_parts(n_rec, bm2_knob("BM2_TEXT_PART", 65536), m->n);      // knob: records that are worth a context of their own (launch policy)
     std::vector<SamFmtJob> jobs((size_t)G);
-    std::vector<int> rcs((size_t)G, 0);
-    std::vector<std::string> msgs((size_t)G);
-    const int all = bm2_host_threads(), budget = all / G > 0 ? all / G : 1;
-    auto lo_of = [&](int g) { return n_rec * g / G; };
-    auto in_parts = [&](auto f) {                                // f(part) on a thread of its own; the first error wins
-        auto one = [&](int g) { bm2_host_thread_budget() = G > 1 ? budget : all; rcs[(size_t)g] = f(g); if (rcs[(size_t)g]) msgs[(size_t)g] = bm2_last_error(); };
-        const int mine = bm2_host_thread_budget();
-        std::vector<std::thread> th;
-        for (int g = 1; g < G; ++g) th.emplace_back(one, g);
-        one(0);
-        for (auto &t : th) t.join();
-        bm2_host_thread_budget() = mine;
-        for (int g = 0; g < G; ++g) if (rcs[(size_t)g]) { bm2_set_error("%s", msgs[(size_t)g].c_str()); return rcs[(size_t)g]; }
-        return 0;
-    };
-    int rc = in_parts([&](int g) {
-        const int64_t lo = lo_of(g), hi = lo_of(g + 1);
+    const int budget = G > 1 ? bm2_part_budget(G) : 0;           // (one part: the caller's own budget)
+    int rc = bm2_run_parts(G, budget, nullptr, [&](int g) {
+        const int64_t lo = bm2_part_lo(n_rec, g, G), hi = bm2_part_lo(n_rec, g + 1, G);
         const int64_t c0 = g ? recs[lo].cigar_off : 0, c1 = g + 1 < G ? recs[hi].cigar_off : n_cigar;
         const int64_t s0 = g ? recs[lo].md_off : 0, s1 = g + 1 < G ? recs[hi].md_off : side_bytes;
         if (c0 < 0 || c1 < c0 || c1 > n_cigar || s0 < 0 || s1 < s0 || s1 > side_bytes) { bm2_set_error("BM2_SAM_F_DEVICE_TEXT: record offsets out of order"); return BM2_EINVAL; }
@@ -430,12 +413,12 @@ int bm2h_dev_text_batch(void *user, const bm2_sam_opt *so, const bm2_reads *read
     *n_out = total;
     if (total > cap) return BM2_ECAP;
     if (!out) { bm2_set_error("BM2_SAM_F_DEVICE_TEXT: no output buffer"); return BM2_EINVAL; }
-    if ((rc = in_parts([&](int g) { return samfmt_finish(m->ctx[g], jobs[(size_t)g], out + at[(size_t)g]); }))) return rc;
+    if ((rc = bm2_run_parts(G, budget, nullptr, [&](int g) { return samfmt_finish(m->ctx[g], jobs[(size_t)g], out + at[(size_t)g]); }))) return rc;
     g_txt_records = (long long)n_rec; g_txt_host = (long long)blob; g_txt_dev = (long long)(total - blob);
     return BM2_OK;
 }
 
-bm2h_text_scope::bm2h_text_scope(bm2_ctx *const *ctx, int n) : one(n == 1 ? ctx[0] : nullptr), tc{ n == 1 ? &one : ctx, n }, hook(bm2h_dev_text_batch, &tc) {
+bm2h_text_scope::bm2h_text_scope(bm2_ctx *const *ctx, int n) : bm2h_ctx_scope(ctx, n), hook(bm2h_dev_text_batch, &tc) {
     for (int g = 0; g < tc.n; ++g) if (tc.ctx[g]) { tc.ctx[g]->tail_enc = nullptr; tc.ctx[g]->tail_enc_bytes = 0; }
 }
 bm2h_text_scope::~bm2h_text_scope() {

@@ -73,6 +73,9 @@ SAM_F_DEVICE_PLAN = 0x08000000      # BM2_SAM_F_DEVICE_PLAN: sam_pe with a conte
 SAM_F_DEVICE_PESTAT = 0x10000000    # BM2_SAM_F_DEVICE_PESTAT: sam_pe with a context and no model given counts the insert sizes on the device (off by default)
 
 
+SAM_F_DEVICE_CGPLAN = 0x20000000    # BM2_SAM_F_DEVICE_CGPLAN: sam_se / sam_pe with a context pick their CIGAR batch with bm2_cigar_plan_dev, no dry emit pass (off by default)
+
+
 class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
     _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
@@ -146,7 +149,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_sam_format_dev", "bm2_sam_text_stats", "bm2_pe_decide", "bm2_pe_decide_dev", "bm2_sam_decide_stats",
            "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats",
            "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats",
-           "bm2_pe_stat", "bm2_pe_stat_dev", "bm2_sam_pestat_stats"]
+           "bm2_pe_stat", "bm2_pe_stat_dev", "bm2_sam_pestat_stats",
+           "bm2_cigar_plan", "bm2_cigar_plan_dev", "bm2_sam_cigar_plan_stats"]
 
 _lib = None
 
@@ -528,6 +532,10 @@ class Context:
         """bm2_pe_stat_dev: see pe_stat()."""
         return pe_stat(None, opt, sam_opt, hits, hit_off, ctx=self, hist=hist, hist_cap=hist_cap)
 
+    def cigar_plan(self, opt, sam_opt, hits, hit_off, plans=None, cap=None):
+        """bm2_cigar_plan_dev: see cigar_plan()."""
+        return cigar_plan(opt, sam_opt, hits, hit_off, plans, ctx=self, cap=cap)
+
     def pe_rescue_queries(self, enc, off, ln, tasks, cap=None):
         """bm2_pe_rescue_queries_dev: see pe_rescue_queries()."""
         return pe_rescue_queries(enc, off, ln, tasks, ctx=self, cap=cap)
@@ -791,6 +799,45 @@ def pe_stat(index_prefix, opt, sam_opt, hits, hit_off, ctx=None, hist=True, hist
         return rc, pes, (h[:room] if hist else None)
     _chk(rc, who)
     return pes, (h[:4 * bins].reshape(4, bins) if hist else None)
+
+
+def sam_cigar_plan_stats():
+    """(lists, hits, selected, lists_heavy) of the last device CIGAR plan (Context.cigar_plan, or a tail with SAM_F_DEVICE_CGPLAN);
+    heavy = the single-end lists, or pairs, that took the wavefront form."""
+    v = [C.c_int64(0) for _ in range(4)]
+    L = lib()
+    L.bm2_sam_cigar_plan_stats.restype = None
+    L.bm2_sam_cigar_plan_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def cigar_plan(opt, sam_opt, hits, hit_off, plans=None, ctx=None, cap=None):
+    """Which hits of decided lists the SAM text asks a CIGAR for (bm2_cigar_plan; with ctx = a Context, with or without an index:
+    bm2_cigar_plan_dev, the same on the device).  hits: ALNREG_DT; hit_off: n_lists + 1 offsets into hits (they may start anywhere);
+    plans = None: single-end lists; a PAIRPLAN_DT array: lists 2p and 2p + 1 are the ends of pair p.
+    -> the selected indices into hits, ascending (int32).
+    cap = a number: ONE call with room for `cap` indices -> (rc, the `cap` slots as the call left them, n_out), nothing raised for BM2_ECAP."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    n_lists = len(hit_off) - 1
+    a = np.ascontiguousarray(hits, ALNREG_DT)
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    pl = None if plans is None else np.ascontiguousarray(plans, PAIRPLAN_DT)
+    room = max(int(hit_off[-1] - hit_off[0]), 0) if cap is None else int(cap)
+    sel = np.full(max(room, 1), -0x11111112, np.int32)
+    n_out = C.c_int64(-1)
+    args = (C.byref(opt), C.byref(so), C.c_int32(n_lists), C.c_void_p(a.ctypes.data if len(a) else None), C.c_void_p(hit_off.ctypes.data),
+            C.c_void_p(pl.ctypes.data if pl is not None else None), C.c_void_p(sel.ctypes.data), C.c_int64(room), C.byref(n_out))
+    if ctx is not None:
+        rc, who = L.bm2_cigar_plan_dev(C.c_void_p(ctx.h), *args), "bm2_cigar_plan_dev"
+    else:
+        rc, who = L.bm2_cigar_plan(*args), "bm2_cigar_plan"
+    if cap is not None:
+        if rc not in (BM2_OK, BM2_ECAP):
+            _chk(rc, who)
+        return rc, sel[:room], n_out.value
+    _chk(rc, who)
+    return sel[:n_out.value].copy()
 
 
 def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, ctx=None, cap=None):

@@ -45,6 +45,9 @@ struct bm2_ctx {
     // workspaces of bm2_pe_rescue_plan_dev / bm2_pe_rescue_queries_dev (plan.hip): lists + offsets, or the mates' codes + the queries'
     // descriptors; counts + places; the tasks, or the queries of the record-level call; a scan
     DevBuf b_pl_in, b_pl_work, b_pl_out, b_pl_scan;
+    // workspaces of bm2_cigar_plan_dev (cgplan.hip): packed hits + offsets + plans + the heavy list; marks + block counts + the heavy
+    // lists' counters; the selection; a scan
+    DevBuf b_cg_in, b_cg_work, b_cg_out, b_cg_scan;
     // What b_pl_in holds since the model's pass of the SAM tail call in progress (pestat.hip), in plan_run's layout: the hits
     // [hbase, hbase + n_hits) of `hits` at 0 and the 2 * n_pairs + 1 re-based offsets of `hit_off` behind them.  epoch = that call's
     // number (bm2h_tail_epoch), 0 = nothing.  plan_run sends neither again when its own arguments are these; whatever else writes

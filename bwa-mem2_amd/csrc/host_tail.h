@@ -166,6 +166,27 @@ struct bm2h_pestat_scope : bm2h_ctx_scope {
     bm2h_pestat_scope(bm2_ctx *const *ctx, int n);
     ~bm2h_pestat_scope();
 };
+// The hits of one chunk whose CIGARs the text will ask for (bm2_cigar_plan_dev's arguments after the context, with the hits packed to the
+// 16 bytes the rule reads: hits[k] is hit hit_off[0] + k, and sel speaks hit_off's numbering).  Set through bm2h_cgplan_hook for the calling
+// thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_CGPLAN, the CIGAR session of bm2h_sam_pe / bm2h_sam_se runs no dry emit: it packs
+// the decided lists on its threads, calls the hook once and fills its batch from sel.  0 = success.
+struct bm2h_cg_mark { int32_t score, secondary, secondary_all, is_alt; };      // 16 B
+typedef int (*bm2h_cgplan_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2h_cg_mark *hits,
+                                    const int64_t *hit_off, const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out);
+struct bm2h_cgplan_hook {
+    bm2h_cgplan_hook(bm2h_cgplan_batch_fn fn, void *user);
+    ~bm2h_cgplan_hook();
+};
+int bm2h_check_list_off(const char *who, int64_t n_lists, const int64_t *hit_off);      // bm2h_check_hit_off over any number of lists
+void bm2h_cgplan_stats_set(long long lists, long long hits, long long selected, long long heavy);
+// The device's hook (cgplan.hip; user = bm2h_text_ctxs: the lists cut into contiguous parts at pair boundaries, one context and host thread
+// per part, the parts' selections appended in order) and its scope.
+int bm2h_dev_cgplan_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2h_cg_mark *hits,
+                          const int64_t *hit_off, const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out);
+struct bm2h_cgplan_scope : bm2h_ctx_scope {
+    bm2h_cgplan_hook hook;
+    bm2h_cgplan_scope(bm2_ctx *const *ctx, int n);
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

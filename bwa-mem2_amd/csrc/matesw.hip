@@ -211,6 +211,7 @@ extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     bm2h_rescue_scope rescue(&c, 1);
     bm2h_plan_scope plan(&c, 1);
     bm2h_pestat_scope model(&c, 1);
+    bm2h_cgplan_scope cgplan(&c, 1);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, dev_rescue_batch, c,
                        bm2_dev_cigar_batch, c);
 }
@@ -275,6 +276,7 @@ extern "C" int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     bm2h_rescue_scope rescue(ctxs, n_ctx);
     bm2h_plan_scope plan(ctxs, n_ctx);
     bm2h_pestat_scope model(ctxs, n_ctx);
+    bm2h_cgplan_scope cgplan(ctxs, n_ctx);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, multi_rescue_batch, &m, multi_cigar_batch, &m);
 }
 extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,
@@ -283,5 +285,6 @@ extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     if (!all_hold_index(ctxs, n_ctx)) { bm2_set_error("bm2_sam_se_dev_multi: every context must hold the index"); return BM2_EINVAL; }
     bm2h_text_ctxs m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
+    bm2h_cgplan_scope cgplan(ctxs, n_ctx);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, multi_cigar_batch, &m);
 }

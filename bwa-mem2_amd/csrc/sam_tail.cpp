@@ -363,6 +363,8 @@ thread_local bm2h_ksw_resident_fn t_planq_fn = nullptr;         // its queries m
 thread_local void *t_plan_user = nullptr;
 thread_local bm2h_pestat_batch_fn t_pestat_fn = nullptr;        // the calling thread's hook (bm2h_pestat_hook)
 thread_local void *t_pestat_user = nullptr;
+thread_local bm2h_cgplan_batch_fn t_cgplan_fn = nullptr;        // the calling thread's hook (bm2h_cgplan_hook)
+thread_local void *t_cgplan_user = nullptr;
 thread_local uint64_t t_tail_epoch = 0;                          // bm2h_tail_epoch()
 std::atomic<uint64_t> g_tail_epoch{0};
 
@@ -1528,7 +1530,44 @@ int cigar_session_batch(const bm2_opt *opt, const bm2_reads *reads, int64_t enc_
     return rc;
 }
 
-RescueStats g_rescue;               // counters of the last bm2_sam_pe call (diagnostic; bm2_sam_rescue_stats)
+void plans_to_c(const std::vector<PairPlan> &plans, int n_pairs, std::vector<bm2_pairplan_t> &out) {
+    if (out.size() < (size_t)n_pairs + 1) out.resize((size_t)n_pairs + 1);
+    for (int pi = 0; pi < n_pairs; ++pi) {
+        const PairPlan &P = plans[(size_t)pi]; bm2_pairplan_t &o = out[(size_t)pi];
+        for (int k = 0; k < 2; ++k) { o.z[k] = P.z[k]; o.n_pri[k] = P.n_pri[k]; o.q_se[k] = P.q_se[k]; }
+        o.extra_flag = P.extra_flag; o.paired = P.paired ? 1 : 0;
+    }
+}
+// BM2_CGPLAN_CHECK=1 (debug; read once): the flag-off tails compare what their dry pass recorded with bm2_cigar_plan on the same lists
+// and fail the call on a difference -- the restatement is the rule as long as this holds.  Hits without a number (pad == 0: rescued
+// ones) are in neither set.
+bool cgplan_check_on() {
+    static const bool on = [] { const char *e = getenv("BM2_CGPLAN_CHECK"); return e && e[0] == '1'; }();
+    return on;
+}
+int cgplan_check(const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int n_lists, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                 const bm2_pairplan_t *plans, const std::vector<std::vector<int32_t>> &recs) {
+    const int64_t tot = hit_off[n_lists];
+    std::vector<int32_t> sel((size_t)tot + 1), want, got;
+    int64_t n_sel = 0;
+    const int rc = bm2_cigar_plan(opt, so, n_lists, hits, hit_off, plans, sel.data(), tot, &n_sel);
+    if (rc) return rc;
+    for (int64_t k = 0; k < n_sel; ++k) { const int32_t pad = hits[sel[(size_t)k]].pad; if (pad > 0) want.push_back(pad - 1); }
+    for (const auto &v : recs) got.insert(got.end(), v.begin(), v.end());
+    std::sort(want.begin(), want.end()); want.erase(std::unique(want.begin(), want.end()), want.end());
+    std::sort(got.begin(), got.end()); got.erase(std::unique(got.begin(), got.end()), got.end());
+    if (want != got) {
+        size_t k = 0;
+        while (k < want.size() && k < got.size() && want[k] == got[k]) ++k;
+        bm2_set_error("%s: BM2_CGPLAN_CHECK: the dry pass asked for %zu hits, bm2_cigar_plan selects %zu; they differ first at position %zu (hit %d against %d)",
+                      who, got.size(), want.size(), k, k < got.size() ? got[k] : -1, k < want.size() ? want[k] : -1);
+        return BM2_EINVAL;
+    }
+    if (getenv("BM2_TAIL_PROF")) fprintf(stderr, "[tail] %-14s cgplan check: %zu hits agree\n", who, got.size());
+    return BM2_OK;
+}
+
+RescueStats g_rescue;              // counters of the last bm2_sam_pe call (diagnostic; bm2_sam_rescue_stats)
 
 struct PeWork {                     // a chunk's working set, kept per calling thread from chunk to chunk: the hit lists (flat store + one
                                     // HitList per read), the rescue batch (tasks in pair order, their flat arrays, the results), the pairs' plans
@@ -1693,14 +1732,101 @@ bm2h_plan_hook::bm2h_plan_hook(bm2h_plan_batch_fn fn, bm2h_ksw_resident_fn qfn, 
 bm2h_plan_hook::~bm2h_plan_hook() { t_plan_fn = nullptr; t_planq_fn = nullptr; t_plan_user = nullptr; }
 bm2h_pestat_hook::bm2h_pestat_hook(bm2h_pestat_batch_fn fn, void *user) { t_pestat_fn = fn; t_pestat_user = user; }
 bm2h_pestat_hook::~bm2h_pestat_hook() { t_pestat_fn = nullptr; t_pestat_user = nullptr; }
+bm2h_cgplan_hook::bm2h_cgplan_hook(bm2h_cgplan_batch_fn fn, void *user) { t_cgplan_fn = fn; t_cgplan_user = user; }
+bm2h_cgplan_hook::~bm2h_cgplan_hook() { t_cgplan_fn = nullptr; t_cgplan_user = nullptr; }
 uint64_t bm2h_tail_epoch() { return t_tail_epoch; }
 
-int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) {
+static std::atomic<long long> g_cp_lists{0}, g_cp_hits{0}, g_cp_sel{0}, g_cp_heavy{0};
+void bm2h_cgplan_stats_set(long long lists, long long hits, long long selected, long long heavy) { g_cp_lists = lists; g_cp_hits = hits; g_cp_sel = selected; g_cp_heavy = heavy; }
+extern "C" void bm2_sam_cigar_plan_stats(int64_t *lists, int64_t *hits, int64_t *selected, int64_t *lists_heavy) {
+    if (lists) *lists = g_cp_lists.load();
+    if (hits) *hits = g_cp_hits.load();
+    if (selected) *selected = g_cp_sel.load();
+    if (lists_heavy) *lists_heavy = g_cp_heavy.load();
+}
+
+int bm2h_check_list_off(const char *who, int64_t n_lists, const int64_t *hit_off) {
     if (hit_off[0] < 0) { bm2_set_error("%s: hit_off[0] is negative", who); return BM2_EINVAL; }
-    for (int64_t i = 0; i < 2 * (int64_t)n_pairs; ++i) {
+    for (int64_t i = 0; i < n_lists; ++i) {
         if (hit_off[i + 1] < hit_off[i]) { bm2_set_error("%s: hit_off decreases at list %lld", who, (long long)i); return BM2_EINVAL; }
         if (hit_off[i + 1] - hit_off[i] > 0x3fffffff) { bm2_set_error("%s: list %lld is too long", who, (long long)i); return BM2_EINVAL; }
     }
+    return BM2_OK;
+}
+int bm2h_check_hit_off(const char *who, int32_t n_pairs, const int64_t *hit_off) { return bm2h_check_list_off(who, 2 * (int64_t)n_pairs, hit_off); }
+
+// ---- which hits the emit half asks reg2aln for (bm2_cigar_plan; the oracle of cgplan.hip): the dry pass of a CIGAR session as a
+// function of its inputs.  One list a[0, n): m[i] = 1 for every hit gen_alt, reg2sam or pe_emit would hand to reg2aln.  plan == NULL: a
+// single-end list (reg2sam); otherwise end `e` of a pair under *plan.  false = an index of the list or the plan points outside it.
+namespace {
+bool cgplan_list(const bm2_opt *opt, const bm2_sam_opt *so, int n, const bm2_alnreg_t *a, const bm2_pairplan_t *plan, int e, uint8_t *m,
+                 std::vector<int> &cnt, std::vector<char> &has_alt) {
+    const bool all = (so->flag & F_ALL) != 0, paired = plan && plan->paired != 0;
+    const int n_pri = plan ? plan->n_pri[e] : 0, z = plan ? plan->z[e] : 0;
+    if (plan && (n_pri < 0 || n_pri > n)) return false;
+    if (paired && (z < 0 || z >= n)) return false;
+    for (int i = 0; i < n; ++i) {
+        if (a[i].secondary >= n && a[i].secondary != INT_MAX) return false;
+        if (a[i].secondary_all >= n) return false;
+        m[i] = 0;
+    }
+    if (!all) {                                                  // gen_alt: both branches of pe_emit reach it, and reg2sam does
+        auto pri_idx = [&](int i) {
+            const int k = a[i].secondary_all;
+            return (k >= 0 && a[i].score >= a[k].score * (double)so->XA_drop_ratio) ? k : -1;
+        };
+        cnt.assign((size_t)n, 0); has_alt.assign((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            const int r = pri_idx(i);
+            if (r >= 0) { ++cnt[(size_t)r]; if (a[i].is_alt) has_alt[(size_t)r] = 1; }
+        }
+        for (int i = 0; i < n; ++i) {
+            const int r = pri_idx(i);
+            if (r < 0) continue;
+            if (cnt[(size_t)r] > so->max_XA_hits_alt || (!has_alt[(size_t)r] && cnt[(size_t)r] > so->max_XA_hits)) continue;
+            m[i] = 1;
+        }
+    }
+    if (paired) {                                                // pe_emit, the paired branch
+        m[z] = 1;
+        if (n_pri < n) { const bm2_alnreg_t *p = &a[n_pri]; if (!(p->score < so->T || p->secondary >= 0 || !p->is_alt)) m[n_pri] = 1; }
+        return true;
+    }
+    if (plan && n > 0) {                                         // pe_emit, no_pairing: the mate's representative
+        if (a[0].score >= so->T) m[0] = 1;
+        else if (n_pri < n && a[n_pri].score >= so->T) m[n_pri] = 1;
+    }
+    for (int k = 0; k < n; ++k) {                                // reg2sam
+        const bm2_alnreg_t *p = &a[k];
+        if (p->score < so->T) continue;
+        if (p->secondary >= 0 && (p->is_alt || !all)) continue;
+        if (p->secondary >= 0 && p->secondary < INT_MAX && p->score < a[p->secondary].score * opt->drop_ratio) continue;
+        m[k] = 1;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int bm2_cigar_plan(const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                              const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out) {
+    if (!opt || !so || n_lists < 0 || !hit_off || !n_out || cap < 0 || (cap > 0 && !sel)) { bm2_set_error("bm2_cigar_plan: bad argument"); return BM2_EINVAL; }
+    if (plans && (n_lists & 1)) { bm2_set_error("bm2_cigar_plan: %d lists with plans (a pair has two)", n_lists); return BM2_EINVAL; }
+    int rc = bm2h_check_list_off("bm2_cigar_plan", n_lists, hit_off);
+    if (rc) return rc;
+    if (hit_off[n_lists] > hit_off[0] && !hits) { bm2_set_error("bm2_cigar_plan: bad argument"); return BM2_EINVAL; }
+    if (hit_off[n_lists] > 0x7fffffff) { bm2_set_error("bm2_cigar_plan: hit numbers beyond 2^31 do not fit sel"); return BM2_EUNSUP; }
+    std::vector<uint8_t> m; std::vector<int> cnt; std::vector<char> has_alt;
+    int64_t got = 0;
+    for (int64_t li = 0; li < n_lists; ++li) {
+        const int64_t b = hit_off[li]; const int n = (int)(hit_off[li + 1] - b);
+        m.resize((size_t)n + 1);
+        if (!cgplan_list(opt, so, n, hits + b, plans ? &plans[li >> 1] : nullptr, (int)(li & 1), m.data(), cnt, has_alt)) {
+            bm2_set_error("bm2_cigar_plan: list %lld has a secondary, secondary_all, z or n_pri that points outside it", (long long)li); return BM2_EINVAL;
+        }
+        for (int i = 0; i < n; ++i) if (m[(size_t)i]) { if (got < cap) sel[got] = (int32_t)(b + i); ++got; }
+    }
+    *n_out = got;
+    if (got > cap) { bm2_set_error("bm2_cigar_plan: %lld hits are selected, room for %lld", (long long)got, (long long)cap); return BM2_ECAP; }
     return BM2_OK;
 }
 
@@ -2142,6 +2268,8 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         if ((so->flag & F_NO_RESCUE) || so->rescue_inline) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PLAN plans the rescue batch: not with MEM_F_NO_RESCUE or rescue_inline"); return BM2_EINVAL; }
     }
     if ((so->flag & BM2_SAM_F_DEVICE_PESTAT) && !t_pestat_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PESTAT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    const bool dev_cgplan = (so->flag & BM2_SAM_F_DEVICE_CGPLAN) != 0;
     const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0, dev_plan = (so->flag & BM2_SAM_F_DEVICE_PLAN) != 0;
     const bool dev_pestat = (so->flag & BM2_SAM_F_DEVICE_PESTAT) != 0 && !pes_in;       // (a model that is given leaves nothing to compute)
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_len || !idx->ann_name) { bm2_set_error("bm2_sam_pe: the index descriptor needs ref_string, contig lengths and names"); return BM2_EINVAL; }
@@ -2523,20 +2651,90 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
             }
             prof.mark("decide scatter");
         }
-        run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
-            Text sink;
-            for (int b; (b = next.fetch_add(1)) < n_blk;) {
-                t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
-                for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
-                    if (!dev_decide) decide(pi, plans[(size_t)pi]);
-                    if (!emit(pi, plans[(size_t)pi], sink)) { int e = -1; failed.compare_exchange_strong(e, pi); }
-                    sink.clear();
-                }
-                t_cg = CgSession();
+        if (dev_cgplan) {
+            // BM2_SAM_F_DEVICE_CGPLAN: no dry emit.  The pairs are decided (here, unless they came decided), the 16 bytes of every hit the
+            // rule reads and the plans go through the hook once, and what comes back names the batch: a selected hit without a number
+            // is a rescued one, which the dry pass skips too.
+            if (!dev_decide) {
+                run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                    for (int b; (b = next.fetch_add(1)) < n_blk;)
+                        for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) decide(pi, plans[(size_t)pi]);
+                    flush_tallies();
+                });
+                next = 0;
             }
-            flush_tallies();
-        });
-        prof.mark("decide + dry emit");
+            prof.mark("decide");
+            static thread_local std::vector<bm2h_cg_mark> packed_of_this_thread;
+            static thread_local std::vector<int64_t> poff_of_this_thread;
+            static thread_local std::vector<int32_t> sel_of_this_thread, pads_of_this_thread;
+            static thread_local std::vector<bm2_pairplan_t> cplans_of_this_thread;
+            std::vector<bm2h_cg_mark> &packed = packed_of_this_thread;
+            std::vector<int32_t> &pads = pads_of_this_thread;      // the hits' numbers beside their packed fields: the selection is turned into batch numbers without a second visit to the lists
+            std::vector<bm2_pairplan_t> &cplans = cplans_of_this_thread;
+            std::vector<int64_t> &poff = poff_of_this_thread;
+            std::vector<int32_t> &sel = sel_of_this_thread;
+            if (poff.size() < (size_t)n + 1) poff.resize((size_t)n + 1);
+            poff[0] = 0;
+            for (int i = 0; i < n; ++i) poff[(size_t)i + 1] = poff[(size_t)i] + lists[i].n;
+            const int64_t tot = poff[(size_t)n];
+            if (packed.size() < (size_t)tot + 1) packed.resize((size_t)tot + 1);
+            if (sel.size() < (size_t)tot + 1) sel.resize((size_t)tot + 1);
+            if (pads.size() < (size_t)tot + 1) pads.resize((size_t)tot + 1);
+            {
+                std::atomic<int> nx(0);
+                run_threads(n_threads < n / 8192 + 1 ? n_threads : n / 8192 + 1, [&]() {
+                    for (int lo; (lo = nx.fetch_add(8192)) < n;)
+                        for (int i = lo; i < n && i < lo + 8192; ++i) {
+                            bm2h_cg_mark *d = packed.data() + poff[(size_t)i];
+                            int32_t *pd = pads.data() + poff[(size_t)i];
+                            const bm2_alnreg_t *a = lists[i].p;
+                            for (int h = 0; h < lists[i].n; ++h) {
+                                d[h].score = a[h].score; d[h].secondary = a[h].secondary; d[h].secondary_all = a[h].secondary_all; d[h].is_alt = a[h].is_alt;
+                                pd[h] = a[h].pad;
+                            }
+                        }
+                });
+            }
+            plans_to_c(plans, n_pairs, cplans);
+            int64_t got = 0;
+            const int rc = t_cgplan_fn(t_cgplan_user, opt, so, n, packed.data(), poff.data(), cplans.data(), sel.data(), tot, &got);
+            if (rc) return rc;
+            recs.resize(1);
+            std::vector<int32_t> &ids = recs[0];
+            ids.reserve((size_t)got);
+            for (int64_t k = 0; k < got; ++k) {
+                const int64_t s = sel[(size_t)k];
+                if (s < 0 || s >= tot) { bm2_set_error("bm2_sam_pe: the CIGAR plan names hit %lld, which no list holds", (long long)s); return BM2_ENODEV; }
+                const int32_t pad = pads[(size_t)s];
+                if (pad > 0) ids.push_back(pad - 1);
+            }
+            prof.mark("cigar plan (device)");
+        } else {
+            run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                Text sink;
+                for (int b; (b = next.fetch_add(1)) < n_blk;) {
+                    t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
+                    for (int pi = b * blk; pi < n_pairs && pi < (b + 1) * blk; ++pi) {
+                        if (!dev_decide) decide(pi, plans[(size_t)pi]);
+                        if (!emit(pi, plans[(size_t)pi], sink)) { int e = -1; failed.compare_exchange_strong(e, pi); }
+                        sink.clear();
+                    }
+                    t_cg = CgSession();
+                }
+                flush_tallies();
+            });
+            prof.mark("decide + dry emit");
+            if (cgplan_check_on()) {                                 // BM2_CGPLAN_CHECK=1: what the dry pass recorded against the rule as bm2_cigar_plan states it
+                std::vector<bm2_alnreg_t> flat; std::vector<int64_t> foff((size_t)n + 1, 0);
+                for (int i = 0; i < n; ++i) foff[(size_t)i + 1] = foff[(size_t)i] + lists[i].n;
+                flat.resize((size_t)foff[(size_t)n] + 1);
+                for (int i = 0; i < n; ++i) if (lists[i].n) memcpy(flat.data() + foff[(size_t)i], lists[i].p, sizeof(bm2_alnreg_t) * (size_t)lists[i].n);
+                std::vector<bm2_pairplan_t> cplans;
+                plans_to_c(plans, n_pairs, cplans);
+                const int rc = cgplan_check("bm2_sam_pe", opt, so, n, flat.data(), foff.data(), cplans.data(), recs);
+                if (rc) return rc;
+            }
+        }
         int64_t enc_bytes = 0;
         for (int i = 0; i < n; ++i) if (reads->off[i] + reads->len[i] > enc_bytes) enc_bytes = reads->off[i] + reads->len[i];
         const int rc = cigar_session_batch(opt, reads, enc_bytes, alnregs, reg_off, recs, cfn, cuser, memo, false);
@@ -2575,6 +2773,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (so->flag & BM2_SAM_F_DEVICE_RESCUE) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_RESCUE is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_PLAN) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PLAN is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_PESTAT) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PESTAT is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);
@@ -2602,18 +2801,51 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         const int blk = 512, n_blk = (n_reads + blk - 1) / blk;
         std::vector<std::vector<int32_t>> recs((size_t)n_blk);
         std::atomic<int> next(0);
-        run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
-            Text sink;
-            for (int b; (b = next.fetch_add(1)) < n_blk;) {
-                t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
-                for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) {
-                    decide(i);
-                    emit(i, sink);
-                    sink.clear();
-                }
-                t_cg = CgSession();
+        if (so->flag & BM2_SAM_F_DEVICE_CGPLAN) {                // no dry emit: decide, pack the 16 bytes a hit the rule reads, one call of the hook
+            TailProf prof("sam_se");
+            run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                for (int b; (b = next.fetch_add(1)) < n_blk;)
+                    for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) decide(i);
+            });
+            prof.mark("decide");
+            const int64_t hb = reg_off[0], tot = reg_off[n_reads] - hb;
+            std::vector<bm2h_cg_mark> packed((size_t)tot + 1);
+            std::vector<int32_t> sel((size_t)tot + 1);
+            {
+                std::atomic<int64_t> nx(0);
+                run_threads(n_threads < tot / 65536 + 1 ? n_threads : (int)(tot / 65536 + 1), [&]() {
+                    for (int64_t lo; (lo = nx.fetch_add(65536)) < tot;)
+                        for (int64_t k = lo; k < tot && k < lo + 65536; ++k) {
+                            const bm2_alnreg_t &a = alnregs[hb + k]; bm2h_cg_mark &d = packed[(size_t)k];
+                            d.score = a.score; d.secondary = a.secondary; d.secondary_all = a.secondary_all; d.is_alt = a.is_alt;
+                        }
+                });
             }
-        });
+            int64_t got = 0;
+            const int rc = t_cgplan_fn(t_cgplan_user, opt, so, n_reads, packed.data(), reg_off, nullptr, sel.data(), tot, &got);
+            if (rc) return rc;
+            recs.resize(1);
+            recs[0].reserve((size_t)got);
+            for (int64_t k = 0; k < got; ++k) { const int32_t pad = alnregs[sel[(size_t)k]].pad; if (pad > 0) recs[0].push_back(pad - 1); }
+            prof.mark("cigar plan (device)");
+        } else {
+            run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                Text sink;
+                for (int b; (b = next.fetch_add(1)) < n_blk;) {
+                    t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
+                    for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) {
+                        decide(i);
+                        emit(i, sink);
+                        sink.clear();
+                    }
+                    t_cg = CgSession();
+                }
+            });
+            if (cgplan_check_on()) {                                 // BM2_CGPLAN_CHECK=1 (see cgplan_check)
+                const int rc = cgplan_check("bm2_sam_se", opt, so, n_reads, alnregs, reg_off, nullptr, recs);
+                if (rc) return rc;
+            }
+        }
         int64_t enc_bytes = 0;
         for (int i = 0; i < n_reads; ++i) if (reads->off[i] + reads->len[i] > enc_bytes) enc_bytes = reads->off[i] + reads->len[i];
         const int rc = cigar_session_batch(opt, reads, enc_bytes, alnregs, reg_off, recs, cfn, cuser, memo, true);

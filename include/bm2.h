@@ -480,6 +480,32 @@ int bm2_pe_stat_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32
  * of hits it uploaded, and how many bytes of hits the plan of the same tail call found resident and did not send again. */
 void bm2_sam_pestat_stats(int64_t *pairs, int64_t *counted, int64_t *hit_bytes_up, int64_t *hit_bytes_shared);
 
+/* ---- the CIGAR batch of a chunk picked without an emit pass (cgplan.hip): WHICH hits the text of decided lists will ask mem_reg2aln
+ * for (bwamem.cpp:1732) -- a function of score, secondary, secondary_all and is_alt of the hits and of the pairs' plans, nothing else.
+ * plans == NULL: n_lists single-end lists, each judged as mem_reg2sam judges it (bwamem.cpp:1521-1577, with mem_gen_alt unless
+ * MEM_F_ALL).  plans != NULL: n_lists is even (BM2_EINVAL otherwise) and lists 2p, 2p + 1 are judged under plans[p] as the emit half of
+ * mem_sam_pe does (bwamem_pair.cpp:487-551): paired -> mem_gen_alt, hit z[i], and hit n_pri[i] when it is a primary ALT hit at or
+ * above T; not paired -> the mate's representative (hit 0 at or above T, else hit n_pri[i] at or above T) and mem_reg2sam.  hit_off
+ * (n_lists + 1 entries) as for bm2_pe_decide; it may start anywhere.  sel receives, ascending, the indices into `hits` (hit_off's
+ * numbering) of the hits asked for, each once; *n_out = their number, BM2_ECAP when cap is smaller (*n_out is complete, nothing is
+ * written at or above cap).  The XA comparison is done in double and the drop_ratio one in float, one operation each, as the host
+ * compiles them.  A secondary (other than INT_MAX) or secondary_all at or beyond its list's length, an n_pri outside [0, n] or, for
+ * a paired pair, a z outside [0, n) is BM2_EINVAL: detected, never followed.  bm2_cigar_plan is the host statement of the rule and
+ * the oracle; bm2_cigar_plan_dev marks and compacts on the device, reads nothing of an index (a context created without one will do)
+ * and handles every list there, whatever its length. */
+int bm2_cigar_plan(const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2_alnreg_t *hits, const int64_t *hit_off,
+                   const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out);
+int bm2_cigar_plan_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2_alnreg_t *hits,
+                       const int64_t *hit_off, const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out);
+/* A library-private bit of bm2_sam_opt.flag, alone or with any of the five bits above: the CIGAR session of bm2_sam_pe_dev,
+ * bm2_sam_se_dev and their _multi forms runs no dry emit pass; the decided lists (16 B a hit) and the plans go through
+ * bm2_cigar_plan_dev's kernels on their context(s) once and the batch is made from what comes back.  Same bytes, same
+ * bm2_sam_cigar_stats.  Off by default.  bm2_sam_se / bm2_sam_pe have no context and answer BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_CGPLAN 0x20000000
+/* of the last bm2_cigar_plan_dev call on this process, or of the last tail with the bit: lists, hits, hits selected, and the lists
+ * (single-end) or pairs that took the wavefront form (more than 16 hits). */
+void bm2_sam_cigar_plan_stats(int64_t *lists, int64_t *hits, int64_t *selected, int64_t *lists_heavy);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

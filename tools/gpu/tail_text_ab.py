@@ -16,6 +16,9 @@ the bytes the plan and the queries move.
 --bit pestat|pestat+plan: BM2_SAM_F_DEVICE_PESTAT (the chunk's insert-size model counted by bm2_pe_stat_dev's kernel) alone and with the
 plan bit, which then reads the hits where the model left them; the result holds bm2_sam_pestat_stats and the bytes the model moves.  The
 phases to read: `sam_pe: pestat` against `sam_pe: pestat (device)`, and `pe_plan_dev: H2D` of --bit plan against --bit pestat+plan.
+--bit cgplan|all+cgplan: BM2_SAM_F_DEVICE_CGPLAN (the CIGAR batch picked by bm2_cigar_plan_dev's kernels, no dry emit pass) alone and with
+the five other bits; the result holds bm2_sam_cigar_plan_stats and the bytes the plan moves.  The phases to read: `sam_pe: decide + dry
+emit` against `sam_pe: decide` + `sam_pe: cigar plan (device)`, and `cigar_session: batch list`.
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -107,7 +110,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan", "cgplan", "all+cgplan"))
     a = ap.parse_args()
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
@@ -132,9 +135,10 @@ def main():
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
-    on = set({"both": "text+decide", "all": "text+decide+rescue"}.get(a.bit, a.bit).split("+"))
+    on = set({"both": "text+decide", "all": "text+decide+rescue", "all+cgplan": "text+decide+rescue+plan+pestat+cgplan"}.get(a.bit, a.bit).split("+"))
     bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if "text" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if "decide" in on else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PESTAT", 0) if "pestat" in on else 0)
+           (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PESTAT", 0) if "pestat" in on else 0) | \
+           (getattr(bm2, "SAM_F_DEVICE_CGPLAN", 0) if "cgplan" in on else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
@@ -145,7 +149,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided, rescued, planned_dev, model_dev = None, None, None, None, None, None
+    counters, first, decided, rescued, planned_dev, model_dev, cgplan_dev = None, None, None, None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -165,6 +169,8 @@ def main():
                 planned_dev = bm2.sam_rescue_plan_stats() + bm2.sam_rescue_stats()
             if v == "on" and "pestat" in on:
                 model_dev = bm2.sam_pestat_stats()
+            if v == "on" and "cgplan" in on:
+                cgplan_dev = bm2.sam_cigar_plan_stats() + bm2.sam_cigar_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -202,6 +208,10 @@ def main():
         pairs, counted, up, shared = model_dev
         mine["pestat_stats"] = {"pairs": pairs, "counted": counted, "hit_bytes_up": up, "hit_bytes_shared": shared}
         mine["pestat_pcie"] = {"up": up + 8 * (2 * pairs + 1), "down": 16 * (so["on"].max_ins + 1), "plan_up_saved": shared + (8 * (2 * pairs + 1) if shared else 0)}
+    if cgplan_dev is not None:                                   # (cgplan.hip: 16 B a hit, 8 B a list offset and 32 B a pair up; 4 B a selected hit down)
+        lists, hits, selected, heavy, planned, used, missed = cgplan_dev
+        mine["cgplan_stats"] = {"lists": lists, "hits": hits, "selected": selected, "lists_heavy": heavy, "planned": planned, "used": used, "missed": missed}
+        mine["cgplan_pcie"] = {"up": 16 * hits + 8 * (lists + 1) + 32 * (lists // 2), "down": 4 * selected + 12}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

@@ -453,6 +453,7 @@ extern "C" bm2_ctx *bm2_create(int device, const bm2_index_desc *idx) {
         ix.ref_len = idx->ref_len; ix.l_pac = idx->l_pac; ix.sentinel_index = idx->sentinel_index;
         for (int i = 0; i < 5; i++) ix.count[i] = idx->count[i] + 1;      // FMI_search.cpp:433-436
         ix.n_seqs = idx->n_seqs;
+        bm2_build_kmer_table(c);                                    // (contexts that share this replica copy `ix`, the table with it)
         c->has_index = true;
         bm2_ensure_subs(c, bm2_knob("BM2_N_SUB", BM2_N_SUB));
     }
@@ -518,7 +519,7 @@ extern "C" void bm2_destroy(bm2_ctx *c) {
     }
     c->subs.clear();
     bm2_batch_destroy(c);
-    void *ps[] = { c->d_cp_occ, c->d_sa_ms, c->d_sa_ls, c->d_ref, c->d_ann_off, c->d_ann_len, c->d_ann_alt, c->d_ann_names, c->d_ann_name_off };
+    void *ps[] = { c->d_cp_occ, c->d_sa_ms, c->d_sa_ls, c->d_ref, c->d_ann_off, c->d_ann_len, c->d_ann_alt, c->d_ann_names, c->d_ann_name_off, c->d_kmer };
     if (!c->is_child) for (void *p : ps) if (p) (void)hipFree(p);          // a shared context does not own the replica
     bm2_release(c->b_pairs); bm2_release(c->b_pairs2); bm2_release(c->b_ref); bm2_release(c->b_qer); bm2_release(c->b_misc); bm2_release(c->b_scan);
     bm2_release(c->b_txt_in); bm2_release(c->b_txt_pos); bm2_release(c->b_txt_out); bm2_release(c->b_txt_enc); bm2_release(c->b_txt_scan);

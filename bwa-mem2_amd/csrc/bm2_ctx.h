@@ -34,6 +34,7 @@ struct bm2_ctx {
     // device copies of the index arrays (owned)
     void *d_cp_occ = nullptr, *d_sa_ms = nullptr, *d_sa_ls = nullptr, *d_ref = nullptr;
     void *d_ann_off = nullptr, *d_ann_len = nullptr, *d_ann_alt = nullptr;
+    void *d_kmer = nullptr;    // the seeding K-mer table (smem.hip: bm2_build_kmer_table); part of the replica
     // contig names for the SAM text kernels (samfmt.hip): the names back to back and n_seqs + 1 offsets; NULL when the descriptor had none
     void *d_ann_names = nullptr, *d_ann_name_off = nullptr;
     // workspaces of bm2_sam_format_dev: inputs (records, ops, side bytes, packed names / qualities), sizes and offsets, the text
@@ -110,7 +111,8 @@ int bm2_ensure_subs(bm2_ctx *c, int n_sub);      // -> parts available (1 + sub-
 static inline int bm2_knob(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }
 
 int  bm2_raise_lds_limit(bm2_ctx *c, int which, const void *kernel, size_t bytes);      // which: a bit number of bm2_ctx::lds_attr_done
-int  bm2_side_streams(bm2_ctx *c);                         // creates the fork / join streams of this context on first use
+void bm2_build_kmer_table(bm2_ctx *c);                     // smem.hip: fills c->d_kmer / c->ix.kmer_tab, kmer_k (0 when off or out of memory); called at index upload
+int  bm2_side_streams(bm2_ctx *c);                       // creates the fork / join streams of this context on first use
 int  bm2_check(hipError_t e, const char *what);            // -> BM2_OK or BM2_ENODEV (+ message)
 void bm2_set_error(const char *fmt, ...);
 int  bm2_reserve(DevBuf &b, size_t bytes);                  // grow-only device allocation

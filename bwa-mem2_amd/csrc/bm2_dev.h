@@ -33,6 +33,8 @@ struct DevIndex {
     int64_t count[5];                // already +1 (FMI_search.cpp:433-436)
     int32_t n_seqs;
     int32_t ref_pk;
+    const uint4 *kmer_tab;           // bi-interval of every string of exactly kmer_k bases (smem.hip: k_kmer_table), pv_pack layout; nullptr = none
+    int32_t kmer_k, pad0;            // 0 = the seeding kernels extend base by base
     __host__ __device__ RefPtr ref(int64_t pos) const { return RefPtr{ref_string, pos, ref_pk}; }
 };
 

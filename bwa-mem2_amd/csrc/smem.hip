@@ -143,7 +143,12 @@ static __device__ __forceinline__ Bi init_bi(const DevIndex &ix, int a) {     //
 enum { W_P1 = 1, W_P2 = 2, W_P3 = 3 };
 enum { SC_P1_ITEM = 0, SC_SLOT1, SC_B1_ITEM, SC_REC, SC_TASK, SC_P2_ITEM, SC_SLOT2, SC_B2_ITEM, SC_P3_ITEM, SC_NEXT, SC_OVF_FLAG,
        SC_POOL, SC_NEXT_W1, SC_NEXT_W2, SC_NEXT_W3, SC_NEXT_B1, SC_NEXT_B2, SC_HEAVY1, SC_HEAVY2, SC_H1_ITEM, SC_H2_ITEM,
-       SC_CONT1, SC_CONT2, SC_C1_ITEM, SC_C2_ITEM, SC_CROWS1, SC_CROWS2, SC_N };   // SC_CONT*: backward tasks k_bwd handed over at a row boundary (SeedBufs::cont1 / cont2), SC_CROWS*: rows k_bwd_cont walked   // SC_NEXT_*: backwardExt calls per kernel           // cursors / counters of the seeding kernels (unsigned long long each)
+       SC_CONT1, SC_CONT2, SC_C1_ITEM, SC_C2_ITEM, SC_CROWS1, SC_CROWS2,
+       // the K-mer table (below): walks that started from an entry / that fell back because the read ends within K bases, an ambiguous base lies in them, the
+       // entry's size is below min_intv; virtual candidates kept on arrival / dropped there for their size, for a size equal to the last kept one's;
+       // tasks that ended with candidates still to arrive; arrivals in k_bwd_heavy; row ends at which a hand-over waited for the last arrival
+       SC_KJ_JUMP, SC_KJ_FB_END, SC_KJ_FB_AMB, SC_KJ_FB_SIZE, SC_KV_KEPT, SC_KV_DROP_SIZE, SC_KV_DROP_EQ, SC_KV_PENDING_END, SC_KV_HEAVY, SC_KV_POSTPONED,
+       SC_N };   // SC_CONT*: backward tasks k_bwd handed over at a row boundary (SeedBufs::cont1 / cont2), SC_CROWS*: rows k_bwd_cont walked   // SC_NEXT_*: backwardExt calls per kernel           // cursors / counters of the seeding kernels (unsigned long long each)
 enum { OVF_SLOT1 = 1, OVF_SLOT2 = 2, OVF_REC = 4, OVF_TASK = 8, OVF_POOL = 16 };
 
 struct __attribute__((aligned(16))) BHead {       // header of a backward-phase task (32 bytes)
@@ -250,14 +255,71 @@ struct QWin {
     }
 };
 
+// ---- the K-mer table: short strings' bi-intervals looked up, not extended -------------------------------------------------
+// tab[code] = the bi-interval (k, l, s) of each of the 4^K strings of exactly K bases (pv_pack layout, 16 bytes; code = sum of base t << 2 t, the
+// string's first base lowest), built on the device at index upload (k_kmer_table).  Passes 1 and 2 use it in two places:
+//   * a forward walk (k_walk<P1>, <P2>) whose first K bases lie inside the read, hold no ambiguous base and have tab[..].s >= min_intv STARTS from that
+//     entry (smn = x + K - 1, j = x + K); it pushes nothing for the lengths below K and tells the backward task so (BHead::pad: n_virtual = K - 1 and
+//     the walk's code in BHead::pad; the list's first K - 1 entries stay empty, so that every index of the list means what it meant);
+//   * the backward phase holds the candidates of forward length 1..K-1 back as VIRTUAL ones: nothing is stored or extended for them until row i = K - j,
+//     where the candidate of forward length j is the string q[x - i, x - i + K) -- one table entry, whose code rolls as the rows go left.  It arrives as
+//     the LAST (shortest) candidate of that row, passes the same in-order test as any other (kept iff s >= min_intv and s != curr_s, int32 as there), is
+//     not extended in that row (the entry IS its state after row i) and is an ordinary candidate from the next row on.  A task ends by `n_curr == 0`
+//     only when no candidate is still to arrive; it is handed over to k_bwd_cont only then, too.
+// Why the records are the reference's, bit for bit:
+//   1. the bi-interval of a string does not depend on the order in which it was extended;
+//   2. sizes only shrink under extension, in either direction, and two candidates of equal size have the same occurrences, so they stay equal under
+//      further backward extension.  A candidate the stepwise code dropped for an equal size in some row (or never pushed, o.s == sms in the walk) has
+//      the size of its nearest longer live candidate when it arrives -- the last size kept in that row -- and is dropped there; if that longer one has
+//      died instead, the arriving one's size is below min_intv too and it is dropped for that.  Conversely one dropped on arrival was dropped
+//      stepwise in that row or before;
+//   3. candidates later in a row never influence earlier ones (curr_s and first_done flow from long to short), and the arriving one is the last;
+//   4. a candidate is never the emitted record while it is virtual or on arrival: its length before the row's extension is at most K - 1.  The
+//      table is used by a call only if K < min_seed_len (bm2_launch_seeding); otherwise every kernel runs stepwise;
+//   5. pass 3 (k_walk<P3>) does not use the table.
+// What changes is the number of extensions executed: n_ext and SC_NEXT_* stay "backwardExt calls executed" and fall below the reference's count.
+static __device__ __forceinline__ uint32_t kmer_pack16(uint64_t lo, uint64_t hi) {      // sixteen bases, one per byte -> two bits each, the first lowest
+    auto p4 = [](uint32_t w) -> uint32_t { const uint32_t x = w & 0x03030303u; return (x | x >> 6 | x >> 12 | x >> 18) & 0xffu; };
+    return p4((uint32_t)lo) | p4((uint32_t)(lo >> 32)) << 8 | p4((uint32_t)hi) << 16 | p4((uint32_t)(hi >> 32)) << 24;
+}
+static __device__ __forceinline__ bool kmer_ambiguous(uint64_t lo, uint64_t hi, int K) {   // a code above 3 among the first K (8 <= K <= 16 ... or fewer) bytes
+    const uint64_t m = 0xfcfcfcfcfcfcfcfcULL;
+    const uint64_t mlo = K >= 8 ? m : m & ((1ULL << (8 * K)) - 1), mhi = K >= 16 ? m : K > 8 ? m & ((1ULL << (8 * (K - 8))) - 1) : 0;
+    return ((lo & mlo) | (hi & mhi)) != 0;
+}
+// one lane per string: init_bi of its last base, then K - 1 backwardExt (one lane fetching both whole entries: build time, not the hot path)
+__global__ void __launch_bounds__(256) k_kmer_table(DevIndex ix, int K, uint4 *__restrict__ tab) {
+    const int64_t code = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (code >= ((int64_t)1 << (2 * K))) return;
+    Bi b = init_bi(ix, (int)((code >> (2 * (K - 1))) & 3));
+    for (int t = K - 2; t >= 0 && b.s > 0; t--) {
+        const int a = (int)((code >> (2 * t)) & 3);
+        const Blk e1 = load_blk(&ix.cp_occ[b.k >> 6]), e2 = load_blk(&ix.cp_occ[(b.k + b.s) >> 6]);
+        const int y1 = (int)(b.k & 63), y2 = (int)((b.k + b.s) & 63);
+        int64_t o1[4], d[4];
+        for (int c = 0; c < 4; c++) {
+            o1[c] = (int64_t)e1.w[c] + __popcll((e1.w[4 + c] >> 1) >> (y1 ^ 63));
+            d[c] = (int64_t)e2.w[c] + __popcll((e2.w[4 + c] >> 1) >> (y2 ^ 63)) - o1[c];
+        }
+        const int64_t sent = (b.k <= ix.sentinel_index && b.k + b.s > ix.sentinel_index) ? 1 : 0;
+        int64_t l = b.l + sent;                                  // FMI_search.cpp:1043-1049
+        for (int c = 3; c > a; c--) l += d[c];
+        b.k = pick4(a, ix.count[0], ix.count[1], ix.count[2], ix.count[3]) + pick4(a, o1[0], o1[1], o1[2], o1[3]);
+        b.l = l;
+        b.s = pick4(a, d[0], d[1], d[2], d[3]);
+    }
+    tab[code] = b.s > 0 ? pv_pack(b.k, b.l, b.s, 0) : make_uint4(0, 0, 0, 0);      // (an empty interval: nobody reads its k and l)
+}
+
 // ---- forward walks ----------------------------------------------------------------------------------------------
 // MODE W_P1: item = read; chain of start positions, every walk leaves a backward task.  W_P2: item = P2Task, one walk.
 // W_P3: item = read; forward-only seeding, SMEM records written directly.
-enum { F_EXT = 0, F_NEWITEM, F_START, F_NEWPOS, F_CHK, F_END, F_DONE };
+enum { F_EXT = 0, F_NEWITEM, F_START, F_NEWPOS, F_CHK, F_END, F_DONE, F_JUMP, F_JUMP2 };      // F_JUMP / F_JUMP2: the walk's first K bases / its table entry are on their way
 
-template <int MODE>
-__global__ void __launch_bounds__(256)
-k_walk(DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc, const int64_t *__restrict__ off,
+// TAB: with the table's states (k_walk_tab) or without them (k_walk: the call runs stepwise, and the kernel is the one it was before the table -- 95 / 102 VGPRs)
+template <int MODE, bool TAB>
+static __device__ __forceinline__ void
+walk_body(const DevIndex &ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc, const int64_t *__restrict__ off,
        const int32_t *__restrict__ len, const P2Task *__restrict__ tasks, int64_t task_cap,
        BHead *__restrict__ heads, uint4 *__restrict__ ents, int64_t slot_cap, uint4 *__restrict__ pool, int pool_cap, int pool_slots,
        bm2_smem_t *__restrict__ recs, int64_t rec_cap, int32_t *__restrict__ smem_cnt, unsigned long long *sc,
@@ -270,6 +332,12 @@ k_walk(DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc,
     __shared__ WavePool pools[4][3];                           // per wave: [0] work items, [1] task slots or records, [2] heavy-task ids
     LdsPool *ip = (LdsPool *)&pools[threadIdx.x >> 6][0], *op = (LdsPool *)&pools[threadIdx.x >> 6][1], *hp = (LdsPool *)&pools[threadIdx.x >> 6][2];
     if ((threadIdx.x & 63) == 0) { ip->pos = ip->end = 0; op->pos = op->end = 0; hp->pos = hp->end = 0; }
+    // the K-mer table (above): K = 0 is the stepwise walk.  Its counters (SC_KJ_*) are kept per workgroup in LDS.
+    const int K = TAB && MODE != W_P3 ? ix.kmer_k : 0;
+    const uint32_t kmask = K > 0 && K < 16 ? (1u << (2 * K)) - 1u : 0xffffffffu;
+    __shared__ unsigned kc[4];
+    if (TAB) { if (threadIdx.x < 4) kc[threadIdx.x] = 0; __syncthreads(); }
+    uint32_t jv = 0;                                           // this walk's code | n_virtual << 28 (0: it did not start from the table); the words on their way travel in eik / eil
     unsigned long long *item_cur = sc + (MODE == W_P1 ? SC_P1_ITEM : MODE == W_P2 ? SC_P2_ITEM : SC_P3_ITEM);
     unsigned long long *out_cur = sc + (MODE == W_P1 ? SC_SLOT1 : MODE == W_P2 ? SC_SLOT2 : SC_REC);
     // work items: it_a = the next item of this lane; its payload is already loaded
@@ -324,7 +392,31 @@ k_walk(DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc,
                 }
                 const Bi b = init_bi(ix, a); smk = b.k; sml = b.l; sms = b.s; smn = x;
                 j = x + 1;
-                if (MODE != W_P3) { n_prev = 0; pool_id = -1; slot = wave_alloc<SLOT_BATCH>(op, out_cur); }
+                if (MODE != W_P3) { n_prev = 0; pool_id = -1; slot = wave_alloc<SLOT_BATCH>(op, out_cur); jv = 0; }
+                state = F_CHK;
+                if (TAB && MODE != W_P3 && K > 0) {
+                    if (x + K > L) atomicAdd(&kc[SC_KJ_FB_END - SC_KJ_JUMP], 1u);
+                    else { eik = (int64_t)load8(q + x); eil = (int64_t)load8(q + x + 8); state = F_JUMP; break; }      // (sixteen bytes from x: the read's bases and, beyond K, whatever follows)
+                }
+            }
+            if (TAB && MODE != W_P3 && state == F_JUMP) {
+                state = F_CHK;
+                if (kmer_ambiguous((uint64_t)eik, (uint64_t)eil, K)) atomicAdd(&kc[SC_KJ_FB_AMB - SC_KJ_JUMP], 1u);
+                else {
+                    jv = kmer_pack16((uint64_t)eik, (uint64_t)eil) & kmask;
+                    const uint4 t = ix.kmer_tab[jv];
+                    eik = (int64_t)((uint64_t)t.x | (uint64_t)t.y << 32); eil = (int64_t)((uint64_t)t.z | (uint64_t)t.w << 32);
+                    state = F_JUMP2; break;
+                }
+            }
+            if (TAB && MODE != W_P3 && state == F_JUMP2) {
+                int64_t tk, tl, ts; int tn;
+                pv_unpack(make_uint4((uint32_t)eik, (uint32_t)((uint64_t)eik >> 32), (uint32_t)eil, (uint32_t)((uint64_t)eil >> 32)), tk, tl, ts, tn);
+                if (ts >= min_intv) {                               // (then every shorter prefix has s >= min_intv as well: the stepwise walk came this far)
+                    smk = tk; sml = tl; sms = ts; smn = x + K - 1; j = x + K; next_x = j;
+                    n_prev = K - 1; jv |= (uint32_t)(K - 1) << 28;                      // the list's first K - 1 entries stay empty: the candidates that arrive in the backward rows
+                    atomicAdd(&kc[0], 1u);
+                } else { jv = 0; atomicAdd(&kc[SC_KJ_FB_SIZE - SC_KJ_JUMP], 1u); }
                 state = F_CHK;
             }
             if (state == F_CHK) {                               // :537-545 / :761-770
@@ -346,7 +438,8 @@ k_walk(DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc,
                         if (hid < heavy_cap) heavy_ids[hid] = (int32_t)slot; else heavy = false;
                     }
                     BHead h; h.rd_off = rd_off; h.r = r; h.L = L; h.x_np = (uint32_t)x | (uint32_t)n_prev << 16;
-                    h.mi_pass = (uint32_t)min_intv | (uint32_t)(MODE == W_P1 ? 1 : 2) << 16 | (heavy ? 1u << 24 : 0u); h.pool_id = pool_id; h.pad = 0;
+                    h.mi_pass = (uint32_t)min_intv | (uint32_t)(MODE == W_P1 ? 1 : 2) << 16 | (heavy ? 1u << 24 : 0u); h.pool_id = pool_id;
+                    h.pad = (int32_t)jv;                            // (n_virtual << 28 | the code of q[x, x + K): the backward rows roll it leftwards)
                     heads[slot] = h;
                 } else ovf |= (MODE == W_P1 ? OVF_SLOT1 : OVF_SLOT2);
                 if (MODE == W_P1) { x = next_x; state = F_NEWPOS; } else state = F_NEWITEM;
@@ -390,20 +483,34 @@ k_walk(DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc,
     atomicAdd(&sc[SC_NEXT], (unsigned long long)n_ext);
     atomicAdd(&sc[SC_NEXT_W1 + (MODE - 1)], (unsigned long long)n_ext);
     if (ovf) atomicOr(&sc[SC_OVF_FLAG], (unsigned long long)ovf);
+    if (TAB) {
+        __syncthreads();
+        if (threadIdx.x < 4 && kc[threadIdx.x]) atomicAdd(&sc[SC_KJ_JUMP + threadIdx.x], (unsigned long long)kc[threadIdx.x]);
+    }
 #ifdef BM2_SMEM_PROF
     atomicAdd(&sc[SC_N + 2 * (MODE - 1)], prof_rounds); atomicAdd(&sc[SC_N + 2 * (MODE - 1) + 1], prof_active);
 #endif
 }
+
+#define WALK_ARGS DevIndex ix, SeedParams sp, int n_reads, const uint8_t *__restrict__ enc, const int64_t *__restrict__ off, const int32_t *__restrict__ len, \
+                  const P2Task *__restrict__ tasks, int64_t task_cap, BHead *__restrict__ heads, uint4 *__restrict__ ents, int64_t slot_cap, uint4 *__restrict__ pool, \
+                  int pool_cap, int pool_slots, bm2_smem_t *__restrict__ recs, int64_t rec_cap, int32_t *__restrict__ smem_cnt, unsigned long long *sc, \
+                  int32_t *__restrict__ heavy_ids, int64_t heavy_cap
+#define WALK_PASS ix, sp, n_reads, enc, off, len, tasks, task_cap, heads, ents, slot_cap, pool, pool_cap, pool_slots, recs, rec_cap, smem_cnt, sc, heavy_ids, heavy_cap
+template <int MODE> __global__ void __launch_bounds__(256) k_walk(WALK_ARGS) { walk_body<MODE, false>(WALK_PASS); }
+// (4 waves per SIMD = the four workgroups per CU the walks are launched with: left alone the register allocation settles at 143 VGPRs, three waves; held to 128 it
+//  spills three words in k_walk_tab<1>, on the path of lists beyond the slot)
+template <int MODE> __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_walk_tab(WALK_ARGS) { walk_body<MODE, true>(WALK_PASS); }
 
 // ---- backward phases --------------------------------------------------------------------------------------------
 // One task = the candidate list of one start position (FMI_search.cpp:586-665).  The list stays where the walk wrote it
 // and is compacted in place: it is read top-down (longest candidate first = the reversal of :586-592), the survivors
 // of a row are written top-down behind the reader, the next candidate is requested while the current one is extended,
 // and the first survivor of a row -- the first candidate of the next row -- never leaves the registers.
-enum { B_EXT = 0, B_NEWITEM, B_FIRST, B_ROWEND, B_ROW, B_FIN, B_DONE };
+enum { B_EXT = 0, B_NEWITEM, B_FIRST, B_ROWEND, B_ROW, B_FIN, B_DONE, B_VROW };      // B_VROW: a row without a real candidate, its arriving one on the way
 
 // LC: survivors of a row kept in LDS per lane (16 B x LC x 256 lanes per block decides how many blocks share a CU's 160 KB)
-template <int LC>
+template <int LC, bool TAB>
 static __device__ __forceinline__ void
 bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__restrict__ enc, const BHead *__restrict__ heads,
          uint4 *__restrict__ ents, int64_t slot_cap, uint4 *__restrict__ pool, int pool_cap, int pool_slots,
@@ -417,6 +524,15 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
     LdsPool *ip = (LdsPool *)&pools[threadIdx.x >> 6][0], *rp = (LdsPool *)&pools[threadIdx.x >> 6][1], *tp = (LdsPool *)&pools[threadIdx.x >> 6][2];
     LdsPool *cp = (LdsPool *)&pools[threadIdx.x >> 6][3];
     if ((threadIdx.x & 63) == 0) { ip->pos = ip->end = 0; rp->pos = rp->end = 0; tp->pos = tp->end = 0; cp->pos = cp->end = 0; }
+    // virtual candidates (the K-mer table, above): v_left of them are still to arrive, one per row; v_code is the code of the last row's string of K bases,
+    // v_raw the entry of this row's, requested when the row's base is known and read at the row's end.  Counters (SC_KV_*) per workgroup in LDS.
+    const int K = TAB ? ix.kmer_k : 0;
+    const uint32_t kmask = K > 0 && K < 16 ? (1u << (2 * K)) - 1u : 0xffffffffu;
+    enum { KV_KEPT = 0, KV_DROP_SIZE, KV_DROP_EQ, KV_PENDING_END, KV_HEAVY_UNUSED, KV_POSTPONED, KV_N };
+    static_assert(SC_KV_KEPT + KV_POSTPONED == SC_KV_POSTPONED && SC_KV_KEPT + KV_PENDING_END == SC_KV_PENDING_END, "the order of the SC_KV_* counters");
+    __shared__ unsigned kc[KV_N];
+    if (TAB) { if (threadIdx.x < KV_N) kc[threadIdx.x] = 0; __syncthreads(); }
+    int v_left = 0; uint32_t v_code = 0; uint4 v_raw = {};
     unsigned long long *item_cur = sc + (pass == 1 ? SC_B1_ITEM : SC_B2_ITEM);
     int64_t it_a = wave_alloc<ITEM_BATCH>(ip, item_cur);
     BHead pl = {};
@@ -465,6 +581,8 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
                 lst = ents + slot * CAPF;
                 lpool = pool + (int64_t)(h.pool_id >= 0 && h.pool_id < pool_slots ? h.pool_id : 0) * pool_cap;
                 top = n_prev - 1; j = x - 1; m_row = x; row0 = true; age = 0;
+                if (TAB) { v_left = (int)((uint32_t)h.pad >> 28); v_code = (uint32_t)h.pad & 0x0fffffffu; }
+                n_prev -= v_left;                               // (the real candidates: the list's entries [v_left, top], at least one)
                 nxt_raw4 = *entry(top);
                 if (j >= 0) w.start(q, j, -1);
                 state = B_FIRST; break;
@@ -473,10 +591,30 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
                 pv_unpack(nxt_raw4, fk, fl, fs, fn);
                 state = B_ROW;
             }
+            if (state == B_VROW) state = B_ROWEND;
             if (state == B_ROWEND) {                            // :650-655
+                if (TAB && v_left > 0) {                        // this row's arrival: q[j, j + K), the row's last and shortest candidate; not extended here
+                    v_left--;
+                    int64_t vk, vl, vs; int vn;
+                    pv_unpack(v_raw, vk, vl, vs, vn);
+                    if (vs < (int64_t)min_intv) atomicAdd(&kc[KV_DROP_SIZE], 1u);
+                    else if (vs == (int64_t)curr_s) atomicAdd(&kc[KV_DROP_EQ], 1u);
+                    else {
+                        curr_s = (int32_t)vs;
+                        vn = j + K - 1;
+                        if (n_curr == 0) { fk = vk; fl = vl; fs = vs; fn = vn; }
+                        else if (n_curr <= LC) surv[(n_curr - 1) * 256 + threadIdx.x] = pv_pack(vk, vl, vs, vn);
+                        else *entry(top - n_curr) = pv_pack(vk, vl, vs, vn);
+                        n_curr++;
+                        atomicAdd(&kc[KV_KEPT], 1u);
+                    }
+                }
                 n_prev = n_curr;
-                if (n_curr == 0) state = B_FIN;
-                else if (export_age > 0 && age >= export_age && j > 0 && n_curr <= CCAP) {
+                const bool want_export = export_age > 0 && age >= export_age && j > 0 && n_curr <= CCAP && n_curr > 0;
+                if (TAB && want_export && v_left > 0) atomicAdd(&kc[KV_POSTPONED], 1u);
+                if (n_curr == 0 && v_left == 0) state = B_FIN;
+                else if (n_curr == 0) { m_row = j; j--; row0 = false; state = B_ROW; }      // nobody alive, somebody still to arrive
+                else if (want_export && v_left == 0) {
                     // HAND-OVER.  A lane-per-task kernel cannot end before its oldest task does, and the task sizes have a long tail (mean ~100
                     // extensions, one in a thousand beyond 1000: tests/seed_sim): the last third of this kernel used to be a few lanes finishing
                     // repeat-rich positions on an otherwise empty GPU.  A task that has had `export_age` extensions stops at the end of its row:
@@ -508,12 +646,15 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
                 else if (a > 3) state = B_FIN;
                 else {
                     n_curr = 0; curr_s = -1; p = 0; first_done = false;
+                    if (TAB && v_left > 0) { v_code = (v_code << 2 | (uint32_t)a) & kmask; v_raw = ix.kmer_tab[v_code]; }      // (back before the row's extensions are)
+                    if (TAB && n_prev == 0) { state = B_VROW; break; }
                     ck = fk; cl = fl; cs = fs; cn = fn;
                     if (n_prev > 1) nxt_raw4 = cand_load(1);
                     state = B_EXT;
                 }
             }
             if (state == B_FIN) {                               // :656-665
+                if (TAB && v_left > 0) atomicAdd(&kc[KV_PENDING_END], 1u);
                 if (n_prev != 0 && (fn - m_row + 1) >= sp.min_seed_len) em = 2;
                 state = B_NEWITEM;
                 if (em) break;                                  // write it out below, then look for work
@@ -569,6 +710,10 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
     atomicAdd(&sc[SC_NEXT], (unsigned long long)n_ext);
     atomicAdd(&sc[SC_NEXT_B1 + (pass - 1)], (unsigned long long)n_ext);
     if (ovf) atomicOr(&sc[SC_OVF_FLAG], (unsigned long long)ovf);
+    if (TAB) {
+        __syncthreads();
+        if (threadIdx.x < KV_N && kc[threadIdx.x]) atomicAdd(&sc[SC_KV_KEPT + threadIdx.x], (unsigned long long)kc[threadIdx.x]);
+    }
 #ifdef BM2_SMEM_PROF
     atomicAdd(&sc[SC_N + 6 + 2 * (pass - 1)], prof_rounds); atomicAdd(&sc[SC_N + 6 + 2 * (pass - 1) + 1], prof_active);
 #endif
@@ -579,9 +724,10 @@ bwd_body(const DevIndex &ix, const SeedParams &sp, int pass, const uint8_t *__re
                  P2Task *__restrict__ tasks, int64_t task_cap, int32_t *__restrict__ smem_cnt, unsigned long long *sc, \
                  CTask *__restrict__ ctasks, int64_t cont_cap, int export_age
 #define BWD_PASS ix, sp, pass, enc, heads, ents, slot_cap, pool, pool_cap, pool_slots, recs, rec_cap, tasks, task_cap, smem_cnt, sc, ctasks, cont_cap, export_age
-template <int LC> __global__ void __launch_bounds__(256) k_bwd(BWD_ARGS) { bwd_body<LC>(BWD_PASS); }
+template <int LC> __global__ void __launch_bounds__(256) k_bwd(BWD_ARGS) { bwd_body<LC, false>(BWD_PASS); }
+template <int LC> __global__ void __launch_bounds__(256) k_bwd_tab(BWD_ARGS) { bwd_body<LC, true>(BWD_PASS); }      // with virtual candidates (the K-mer table): 144 VGPRs against 127
 // the same with the register allocation told to leave room for 5 waves per SIMD (96 VGPRs, 100 bytes per lane spilled)
-template <int LC> __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_bwd5(BWD_ARGS) { bwd_body<LC>(BWD_PASS); }
+template <int LC> __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_bwd5(BWD_ARGS) { bwd_body<LC, false>(BWD_PASS); }
 // Measured in round 5 and removed (profiles/r05b_sweep.json, r05c_sweep_slow_rounds.json, r05h_sweep_kmer_table_pass3.json): (0) a k-mer table (the
 // bi-interval of every string of up to 12 bases, 537 MB, built on the device at index upload -- the interval of a string does not depend on the order it was
 // extended in, checked with the oracle on 2 M strings) from which pass 3's walks took their first 9..12 bases in one lookup: bit-exact, 40 % fewer rounds in
@@ -607,8 +753,9 @@ static __device__ __forceinline__ void wave_sync() {
 // (-> at most one SMEM per row, and only if that first one died), and a live candidate is kept iff its interval size
 // differs from the previous LIVE candidate's (equal to the reference's compare with the last kept size, truncated to
 // int32 as there: a dropped candidate has the size of the last kept one).  The list sits in LDS, compacted in place.
-__global__ void __launch_bounds__(256)
-k_bwd_heavy(DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ enc, const BHead *__restrict__ heads,
+template <bool TAB>
+static __device__ __forceinline__ void
+heavy_body(const DevIndex &ix, SeedParams sp, int pass, const uint8_t *__restrict__ enc, const BHead *__restrict__ heads,
             const uint4 *__restrict__ ents, int64_t slot_cap, const uint4 *__restrict__ pool, int pool_cap, int pool_slots,
             const int32_t *__restrict__ heavy_ids, int64_t heavy_cap,
             bm2_smem_t *__restrict__ recs, int64_t rec_cap, P2Task *__restrict__ tasks, int64_t task_cap,
@@ -627,6 +774,9 @@ k_bwd_heavy(DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ en
     int64_t n_ext = 0;
     unsigned ovf = 0;
     const unsigned long long lt_mask = lane ? (~0ULL >> (64 - lane)) : 0ULL;
+    const int K = TAB ? ix.kmer_k : 0;
+    const uint32_t kmask = K > 0 && K < 16 ? (1u << (2 * K)) - 1u : 0xffffffffu;
+    unsigned n_varr = 0;                                         // arrivals of virtual candidates (the same in every lane; lane 0 reports)
     for (;;) {
         // one item per wavefront.  EVERY lane executes the atomic (lane 0 adds 1, the others 0) and the body sits in an `if`, not
         // behind a `continue`: with `if (lane == 0) it = atomicAdd(...)` + `continue` the compiler may structurise the loop so
@@ -645,16 +795,20 @@ k_bwd_heavy(DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ en
         const uint4 *src = ents + (int64_t)slot * CAPF;
         const uint4 *psrc = pool + (int64_t)(h.pool_id >= 0 && h.pool_id < pool_slots ? h.pool_id : 0) * pool_cap;
         const int top = n_prev - 1;
+        int v_left = TAB ? (int)((uint32_t)h.pad >> 28) : 0; uint32_t v_code = (uint32_t)h.pad & 0x0fffffffu;      // virtual candidates (the K-mer table, above): one arrives per row
+        n_prev -= v_left;                                        // (the list's first v_left entries are empty: n_prev + v_left <= HCAP holds for every row)
         for (int d = lane; d < n_prev; d += 64) {                // longest first (:586-592) = the walk's list read top-down
             const int idx = top - d;
             lst[d] = idx < CAPF ? src[idx] : psrc[idx - CAPF];
         }
         wave_sync();
         int m_row = x;
-        for (int j = x - 1; j >= 0 && n_prev > 0; j--) {          // :596-655
+        for (int j = x - 1; j >= 0 && (n_prev > 0 || v_left > 0); j--) {          // :596-655
             const int a = q[j];
             if (a > 3) break;
             int n_curr = 0; bool first_done = false; int32_t curr_s = -1;
+            uint4 v_raw = {};
+            if (TAB && v_left > 0) { v_code = (v_code << 2 | (uint32_t)a) & kmask; v_raw = ix.kmer_tab[v_code]; }      // (every lane the same entry: one request)
             for (int c0 = 0; c0 < n_prev; c0 += 64) {
                 const int d = c0 + lane;
                 const bool valid = d < n_prev;
@@ -695,6 +849,17 @@ k_bwd_heavy(DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ en
                 if (am) curr_s = as[__popcll(am) - 1];
                 wave_sync();
             }
+            if (TAB && v_left > 0) {                             // this row's arrival joins the list behind the row's ballots; it is not extended here
+                v_left--;
+                int64_t vk, vl, vs; int vn;
+                pv_unpack(v_raw, vk, vl, vs, vn);
+                if (vs >= min_intv && vs != (int64_t)curr_s) {
+                    if (lane == 0) lst[n_curr] = pv_pack(vk, vl, vs, j + K - 1);
+                    n_curr++;
+                }
+                n_varr++;
+                wave_sync();
+            }
             n_prev = n_curr;
             m_row = j;
         }
@@ -723,7 +888,15 @@ k_bwd_heavy(DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ en
     atomicAdd(&sc[SC_NEXT], (unsigned long long)n_ext);
     atomicAdd(&sc[SC_NEXT_B1 + (pass - 1)], (unsigned long long)n_ext);
     if (ovf) atomicOr(&sc[SC_OVF_FLAG], (unsigned long long)ovf);
+    if (TAB && lane == 0 && n_varr) atomicAdd(&sc[SC_KV_HEAVY], (unsigned long long)n_varr);
 }
+#define HEAVY_ARGS DevIndex ix, SeedParams sp, int pass, const uint8_t *__restrict__ enc, const BHead *__restrict__ heads, const uint4 *__restrict__ ents, int64_t slot_cap, \
+                   const uint4 *__restrict__ pool, int pool_cap, int pool_slots, const int32_t *__restrict__ heavy_ids, int64_t heavy_cap, bm2_smem_t *__restrict__ recs, \
+                   int64_t rec_cap, P2Task *__restrict__ tasks, int64_t task_cap, int32_t *__restrict__ smem_cnt, unsigned long long *sc
+#define HEAVY_PASS ix, sp, pass, enc, heads, ents, slot_cap, pool, pool_cap, pool_slots, heavy_ids, heavy_cap, recs, rec_cap, tasks, task_cap, smem_cnt, sc
+__global__ void __launch_bounds__(256) k_bwd_heavy(HEAVY_ARGS) { heavy_body<false>(HEAVY_PASS); }
+// (80 VGPRs: one wavefront of this kernel per SIMD beside three of k_bwd_tab's, 3 x 144 + 80 of 512, as 3 x 128 + 72 without the table)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) k_bwd_heavy_tab(HEAVY_ARGS) { heavy_body<true>(HEAVY_PASS); }
 
 // ---- the tasks k_bwd handed over: SIXTEEN LANES per task, four tasks per wavefront ---------------------------------------------
 // A handed-over task has had its share of a lane (BM2_BWD_EXPORT_AGE extensions) and still has rows to go -- a few candidates over tens of rows,
@@ -1146,6 +1319,12 @@ int bm2_launch_seeding(bm2_ctx *c, const SeedParams &sp, int n_reads, const uint
                        void (*tick)(bm2_ctx *, const char *), int max_len) {
     if (bm2_side_streams(c)) return BM2_ENODEV;
     hipStream_t s = c->stream, s3 = c->side_stream[0], sh = c->side_stream[1];
+    // the K-mer table serves this call only if a string of K bases is too short to be a seed (rule 4 of the table's comment); else: stepwise, as without a table
+    // (nor with BM2_BWD_WAVES >= 5, a measurement knob whose kernels exist without the table only).  A stepwise call launches the kernels without the table's
+    // states: the ont2d options' min_seed_len is 14, and their walks lose 15 % to the table kernels' registers (profiles/seed_kmer_ab.json)
+    DevIndex ixs = c->ix;
+    if (!(ixs.kmer_tab && ixs.kmer_k > 0 && ixs.kmer_k < sp.min_seed_len) || bm2_knob("BM2_BWD_WAVES", 4) >= 5) { ixs.kmer_k = 0; ixs.kmer_tab = nullptr; }
+    const bool tab = ixs.kmer_k > 0;
     // workgroups per CU of the wavefront-per-task kernel beside k_bwd: 12 (pass 1's backward phase 14.9 -> 14.2 ms, profiles/r06e_sweep_bwd_heavy_stream_grid.json;
     // 1 / 2 / 4 / 8 per CU and a side stream on another hardware queue than the main stream's: all within 0.3 ms of each other)
     const int grid_heavy = c->n_cu * bm2_knob("BM2_BWD_HEAVY_WG", 12);
@@ -1161,7 +1340,7 @@ int bm2_launch_seeding(bm2_ctx *c, const SeedParams &sp, int n_reads, const uint
     auto launch_p3 = [&]() {
         (void)hipEventRecord(c->ev_fork, s);
         (void)hipStreamWaitEvent(s3, c->ev_fork, 0);
-        hipLaunchKernelGGL(k_walk<W_P3>, dim3(grid_p3), dim3(256), 0, s3, c->ix, sp, n_reads, enc, off, len, (const P2Task *)nullptr, (int64_t)0,
+        hipLaunchKernelGGL(k_walk<W_P3>, dim3(grid_p3), dim3(256), 0, s3, ixs, sp, n_reads, enc, off, len, (const P2Task *)nullptr, (int64_t)0,
                            (BHead *)nullptr, (uint4 *)nullptr, (int64_t)0, (uint4 *)nullptr, 0, 0, sb.recs, sb.rec_cap, smem_cnt, sc,
                            (int32_t *)nullptr, (int64_t)0);
         (void)hipEventRecord(c->ev_join[0], s3);
@@ -1173,10 +1352,10 @@ int bm2_launch_seeding(bm2_ctx *c, const SeedParams &sp, int n_reads, const uint
         const int64_t slot_cap = pass == 1 ? sb.slot1_cap : sb.slot2_cap;
         int32_t *heavy = pass == 1 ? sb.heavy1 : sb.heavy2;
         if (pass == 1)
-            hipLaunchKernelGGL(k_walk<W_P1>, dim3(grid_walk), dim3(256), 0, s, c->ix, sp, n_reads, enc, off, len, (const P2Task *)nullptr, (int64_t)0,
+            hipLaunchKernelGGL(tab ? k_walk_tab<W_P1> : k_walk<W_P1>, dim3(grid_walk), dim3(256), 0, s, ixs, sp, n_reads, enc, off, len, (const P2Task *)nullptr, (int64_t)0,
                                heads, ents, slot_cap, sb.pool, sb.pool_cap, sb.pool_slots, sb.recs, sb.rec_cap, smem_cnt, sc, heavy, sb.heavy_cap);
         else
-            hipLaunchKernelGGL(k_walk<W_P2>, dim3(grid_walk), dim3(256), 0, s, c->ix, sp, n_reads, enc, off, len, sb.tasks, sb.task_cap,
+            hipLaunchKernelGGL(tab ? k_walk_tab<W_P2> : k_walk<W_P2>, dim3(grid_walk), dim3(256), 0, s, ixs, sp, n_reads, enc, off, len, sb.tasks, sb.task_cap,
                                heads, ents, slot_cap, sb.pool, sb.pool_cap, sb.pool_slots, sb.recs, sb.rec_cap, smem_cnt, sc, heavy, sb.heavy_cap);
         tick(c, pass == 1 ? "smem.walk1" : "smem.walk2");
         if (p3_at == pass) launch_p3();
@@ -1184,20 +1363,21 @@ int bm2_launch_seeding(bm2_ctx *c, const SeedParams &sp, int n_reads, const uint
         {       // (after k_bwd instead of beside it: +1 ms per pass, profiles/r05b_sweep.json)
             (void)hipEventRecord(c->ev_join[2], s);
             (void)hipStreamWaitEvent(sh, c->ev_join[2], 0);
-            hipLaunchKernelGGL(k_bwd_heavy, dim3(grid_heavy), dim3(256), 0, sh, c->ix, sp, pass, enc, heads, ents, slot_cap, sb.pool, sb.pool_cap,
+            hipLaunchKernelGGL(tab ? k_bwd_heavy_tab : k_bwd_heavy, dim3(grid_heavy), dim3(256), 0, sh, ixs, sp, pass, enc, heads, ents, slot_cap, sb.pool, sb.pool_cap,
                                sb.pool_slots, heavy, sb.heavy_cap, sb.recs, sb.rec_cap, sb.tasks, sb.task_cap, smem_cnt, sc);
             (void)hipEventRecord(c->ev_join[1], sh);
         }
         const int lc = bm2_knob("BM2_BWD_LCAP", LCAP), wpe = bm2_knob("BM2_BWD_WAVES", 4);
         auto kb = wpe >= 5 ? (lc <= 4 ? k_bwd5<4> : k_bwd5<6>)
+                  : tab    ? (lc <= 4 ? k_bwd_tab<4> : lc <= 6 ? k_bwd_tab<6> : lc <= 8 ? k_bwd_tab<8> : k_bwd_tab<LCAP>)
                            : (lc <= 4 ? k_bwd<4> : lc <= 6 ? k_bwd<6> : lc <= 8 ? k_bwd<8> : k_bwd<LCAP>);
         CTask *cont = (CTask *)(pass == 1 ? sb.cont1 : sb.cont2);
-        hipLaunchKernelGGL(kb, dim3(grid_bwd), dim3(256), 0, s, c->ix, sp, pass, enc, heads, ents, slot_cap, sb.pool, sb.pool_cap,
+        hipLaunchKernelGGL(kb, dim3(grid_bwd), dim3(256), 0, s, ixs, sp, pass, enc, heads, ents, slot_cap, sb.pool, sb.pool_cap,
                            sb.pool_slots, sb.recs, sb.rec_cap, sb.tasks, sb.task_cap, smem_cnt, sc, cont, sb.cont_cap, export_age);
         (void)hipStreamWaitEvent(s, c->ev_join[1], 0);
         tick(c, pass == 1 ? "smem.bwd1" : "smem.bwd2");
         if (export_age > 0) {                                   // the tasks k_bwd handed over, sixteen lanes each (they may file pass-2 tasks: before k_walk<P2>)
-            hipLaunchKernelGGL(k_bwd_cont, dim3(c->n_cu * bm2_knob("BM2_BWD_CONT_BPC", 6)), dim3(256), 0, s, c->ix, sp, pass, enc, ents, slot_cap, sb.pool, sb.pool_cap,
+            hipLaunchKernelGGL(k_bwd_cont, dim3(c->n_cu * bm2_knob("BM2_BWD_CONT_BPC", 6)), dim3(256), 0, s, ixs, sp, pass, enc, ents, slot_cap, sb.pool, sb.pool_cap,
                                sb.pool_slots, cont, sb.cont_cap, sb.recs, sb.rec_cap, sb.tasks, sb.task_cap, smem_cnt, sc);
             tick(c, pass == 1 ? "smem.cont1" : "smem.cont2");
         }
@@ -1222,6 +1402,34 @@ int bm2_launch_smem_finish(bm2_ctx *c, int n_reads, const SeedBufs &sb, const un
     { const int rc_a = bm2_raise_lds_limit(c, 1, (const void *)k_smem_finish_big, lds); if (rc_a) return rc_a; }
     hipLaunchKernelGGL(k_smem_finish_big, dim3(c->n_cu), dim3(256), lds, c->stream, tmp, smem_cnt, smem_off, max_occ, out, occ_cnt, big_list, big_cnt, big_cur, keys_arg);
     return bm2_check(hipGetLastError(), "k_smem_finish launch");
+}
+// The K-mer table of a replica, made when the index has been uploaded.  K: BM2_SEED_KMER (0 = no table), else from the index's size: the largest K at which a
+// string of K bases still has KMER_AUTO_OCC expected occurrences on the two strands -- 14 at 3100 Mbp (23 occurrences), the best of 11..14 measured there
+// (profiles/seed_kmer_ab.json: 56.8 ms per step without, 51.3 / 50.0 / 48.3 / 46.9 ms with K = 11 / 12 / 13 / 14) -- and none below K = 10 or below
+// KMER_AUTO_MIN_LEN bases on the two strands (a 64 Mbp reference): there the Occ table sits in the last-level cache and a table would only cost upload
+// time.  No memory for it is not an error: the kernels extend base by base then.
+#define KMER_AUTO_OCC 16.0
+#define KMER_AUTO_MIN_LEN ((int64_t)128 << 20)
+#define KMER_MAX 14                                             // (a code and n_virtual share 32 bits of a task's header; 4^14 entries are 4.3 GB)
+void bm2_build_kmer_table(bm2_ctx *c) {
+    c->ix.kmer_tab = nullptr; c->ix.kmer_k = 0;
+    int K = 0;
+    while (K < KMER_MAX && (double)c->ix.ref_len / (double)((int64_t)1 << (2 * (K + 1))) >= KMER_AUTO_OCC) K++;
+    if (K < 10 || c->ix.ref_len < KMER_AUTO_MIN_LEN) K = 0;
+    K = bm2_knob("BM2_SEED_KMER", K);
+    if (K < 2) return;
+    if (K > KMER_MAX) K = KMER_MAX;
+    const int64_t n = (int64_t)1 << (2 * K);
+    if (hipMalloc(&c->d_kmer, (size_t)n * sizeof(uint4)) != hipSuccess) { (void)hipGetLastError(); c->d_kmer = nullptr; return; }
+    timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    hipLaunchKernelGGL(k_kmer_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->ix, K, (uint4 *)c->d_kmer);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(c->d_kmer); c->d_kmer = nullptr; return; }
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    if (getenv("BM2_VERBOSE") || bm2_knob("BM2_SEED_KMER_LOG", 0))
+        fprintf(stderr, "[index] k-mer table: K = %d, %lld bytes, built in %.1f ms\n", K, (long long)(n * (int64_t)sizeof(uint4)),
+                (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6);
+    c->ix.kmer_tab = (const uint4 *)c->d_kmer; c->ix.kmer_k = K;
 }
 int bm2_seed_sizes(size_t *head, size_t *ent, size_t *task, int *n_sc, size_t *ctask) {
     *head = sizeof(BHead); *ent = (size_t)CAPF * 16; *task = sizeof(P2Task); *n_sc = SC_N + 10; *ctask = sizeof(CTask);

@@ -76,6 +76,9 @@ SAM_F_DEVICE_PESTAT = 0x10000000    # BM2_SAM_F_DEVICE_PESTAT: sam_pe with a con
 SAM_F_DEVICE_CGPLAN = 0x20000000    # BM2_SAM_F_DEVICE_CGPLAN: sam_se / sam_pe with a context pick their CIGAR batch with bm2_cigar_plan_dev, no dry emit pass (off by default)
 
 
+SAM_F_DEVICE_SEMARK = 0x40000000    # BM2_SAM_F_DEVICE_SEMARK: sam_se with a context marks the primary hits of its lists with bm2_se_mark_dev, one call a chunk (off by default)
+
+
 class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
     _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
@@ -150,7 +153,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_pe_rescue_plan", "bm2_pe_rescue_apply", "bm2_pe_rescue_apply_dev", "bm2_sam_rescue_apply_stats",
            "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats",
            "bm2_pe_stat", "bm2_pe_stat_dev", "bm2_sam_pestat_stats",
-           "bm2_cigar_plan", "bm2_cigar_plan_dev", "bm2_sam_cigar_plan_stats"]
+           "bm2_cigar_plan", "bm2_cigar_plan_dev", "bm2_sam_cigar_plan_stats",
+           "bm2_se_mark", "bm2_se_mark_dev", "bm2_sam_se_mark_stats"]
 
 _lib = None
 
@@ -536,6 +540,10 @@ class Context:
         """bm2_cigar_plan_dev: see cigar_plan()."""
         return cigar_plan(opt, sam_opt, hits, hit_off, plans, ctx=self, cap=cap)
 
+    def se_mark(self, opt, sam_opt, hits, hit_off, first_id=0):
+        """bm2_se_mark_dev: see se_mark()."""
+        return se_mark(opt, sam_opt, hits, hit_off, first_id, ctx=self)
+
     def pe_rescue_queries(self, enc, off, ln, tasks, cap=None):
         """bm2_pe_rescue_queries_dev: see pe_rescue_queries()."""
         return pe_rescue_queries(enc, off, ln, tasks, ctx=self, cap=cap)
@@ -838,6 +846,37 @@ def cigar_plan(opt, sam_opt, hits, hit_off, plans=None, ctx=None, cap=None):
         return rc, sel[:room], n_out.value
     _chk(rc, who)
     return sel[:n_out.value].copy()
+
+
+def sam_se_mark_stats():
+    """(lists, hits, lists_heavy) of the last device marking (Context.se_mark, or a tail with SAM_F_DEVICE_SEMARK); heavy = the lists that
+    took the wavefront form."""
+    v = [C.c_int64(0) for _ in range(3)]
+    L = lib()
+    L.bm2_sam_se_mark_stats.restype = None
+    L.bm2_sam_se_mark_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def se_mark(opt, sam_opt, hits, hit_off, first_id=0, ctx=None):
+    """Which hits of single-end lists are primary (bm2_se_mark: mem_mark_primary_se, and mem_reorder_primary5 under MEM_F_PRIMARY5; with
+    ctx = a Context, with or without an index: bm2_se_mark_dev, the same on the device).  hits: a C-contiguous ALNREG_DT array, reordered
+    and annotated IN PLACE; hit_off: n_lists + 1 offsets into hits (they may start anywhere); list i has the id first_id + i.
+    -> n_pri (int32 per list): its hits on the primary assembly."""
+    L = lib()
+    hit_off = np.ascontiguousarray(hit_off, np.int64)
+    n_lists = len(hit_off) - 1
+    if not (isinstance(hits, np.ndarray) and hits.dtype == ALNREG_DT and hits.flags["C_CONTIGUOUS"] and hits.flags["WRITEABLE"]):
+        raise TypeError("se_mark works in place: hits must be a writeable C-contiguous ALNREG_DT array")
+    so = sam_opt if sam_opt is not None else default_sam_opt()
+    n_pri = np.full(max(n_lists, 1), -0x11111112, np.int32)
+    args = (C.byref(opt), C.byref(so), C.c_int32(n_lists), C.c_void_p(hits.ctypes.data if len(hits) else None), C.c_void_p(hit_off.ctypes.data),
+            C.c_int64(first_id), C.c_void_p(n_pri.ctypes.data))
+    if ctx is not None:
+        _chk(L.bm2_se_mark_dev(C.c_void_p(ctx.h), *args), "bm2_se_mark_dev")
+    else:
+        _chk(L.bm2_se_mark(*args), "bm2_se_mark")
+    return n_pri[:n_lists]
 
 
 def pe_rescue_plan(index_prefix, opt, sam_opt, hits, hit_off, read_len, pes, ctx=None, cap=None):

@@ -49,6 +49,9 @@ struct bm2_ctx {
     // workspaces of bm2_cigar_plan_dev (cgplan.hip): packed hits + offsets + plans + the heavy list; marks + block counts + the heavy
     // lists' counters; the selection; a scan
     DevBuf b_cg_in, b_cg_work, b_cg_out, b_cg_scan;
+    // workspaces of bm2_se_mark_dev (semark.hip): packed hits + offsets; results + n_pri + the 16 bytes a hit the CIGAR plan reads;
+    // binning + the heavy list + the long lists' working records; two scans
+    DevBuf b_sm_in, b_sm_out, b_sm_work, b_sm_scan, b_sm_scan2;
     // What b_pl_in holds since the model's pass of the SAM tail call in progress (pestat.hip), in plan_run's layout: the hits
     // [hbase, hbase + n_hits) of `hits` at 0 and the 2 * n_pairs + 1 re-based offsets of `hit_off` behind them.  epoch = that call's
     // number (bm2h_tail_epoch), 0 = nothing.  plan_run sends neither again when its own arguments are these; whatever else writes

@@ -188,8 +188,11 @@ __global__ __launch_bounds__(256) void k_cg_write(const uint8_t *__restrict__ ma
 namespace {
 // The selection of one batch on one context.  hits[k] is hit hit_off[0] + k (packed); hit_off has n_lists + 1 checked entries and may
 // start anywhere; sel speaks its numbering.  *heavy = units that took the wavefront form.
+// d_hits / d_off != NULL: the resident form -- the packed hits and the offsets from 0 lie in HBM already (semark.hip's kernels left them),
+// `hits` is not read and neither is uploaded.
 int cgplan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2h_cg_mark *hits, const int64_t *hit_off,
-               const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out, int64_t *heavy, int64_t first_unit = 0) {
+               const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out, int64_t *heavy, int64_t first_unit = 0,
+               const bm2h_cg_mark *d_hits = nullptr, const int64_t *d_off = nullptr) {
     *n_out = 0; *heavy = 0;
     if (n_lists == 0) return BM2_OK;
     if (hit_off[n_lists] > 0x7fffffff) { bm2_set_error("%s: hit numbers beyond 2^31 do not fit sel", who); return BM2_EUNSUP; }
@@ -212,7 +215,7 @@ int cgplan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     }
     const int64_t n_heavy = (int64_t)heavy_list.size(), nb = (n_hits + CG_BLOCK_HITS - 1) / CG_BLOCK_HITS, room = cap < n_hits ? cap : n_hits;
     prof.mark("pack");
-    const size_t in_b = up256((size_t)n_hits * sizeof(bm2h_cg_mark)), off_b = up256((size_t)(n_lists + 1) * 8), plan_b = up256(plans ? (size_t)n_units * sizeof(bm2_pairplan_t) : 0),
+    const size_t in_b = d_hits ? 0 : up256((size_t)n_hits * sizeof(bm2h_cg_mark)), off_b = up256((size_t)(n_lists + 1) * 8), plan_b = up256(plans ? (size_t)n_units * sizeof(bm2_pairplan_t) : 0),
                  hl_b = up256((size_t)n_heavy * 4), hw_b = up256((size_t)n_heavy * 8);
     const size_t mark_b = up256((size_t)n_hits + 4), stat_b = 256, bcnt_b = up256((size_t)(nb + 1) * 4), boff_b = up256((size_t)(nb + 2) * 8), work_b = up256((size_t)work_words * 4);
     if ((rc = bm2_reserve(c->b_cg_in, in_b + off_b + plan_b + hl_b + hw_b + 256))) return rc;
@@ -221,7 +224,7 @@ int cgplan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     char *d = (char *)c->b_cg_in.p, *w = (char *)c->b_cg_work.p;
     CgPrm P;
     memset(&P, 0, sizeof P);
-    P.hits = (const bm2h_cg_mark *)d; P.hit_off = (const int64_t *)(d + in_b); P.plans = plans ? (const bm2_pairplan_t *)(d + in_b + off_b) : nullptr;
+    P.hits = d_hits ? d_hits : (const bm2h_cg_mark *)d; P.hit_off = d_off ? d_off : (const int64_t *)(d + in_b); P.plans = plans ? (const bm2_pairplan_t *)(d + in_b + off_b) : nullptr;
     P.heavy_list = (const int32_t *)(d + in_b + off_b + plan_b); P.heavy_work = (const int64_t *)(d + in_b + off_b + plan_b + hl_b);
     P.mark = (uint8_t *)w; P.stat = (int32_t *)(w + mark_b);
     int32_t *d_bcnt = (int32_t *)(w + mark_b + stat_b);
@@ -231,8 +234,8 @@ int cgplan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     P.n_units = (int32_t)n_units; P.n_heavy = (int32_t)n_heavy; P.per_unit = per_unit; P.T = so->T; P.all = (so->flag & CG_F_ALL) != 0;
     P.max_xa = so->max_XA_hits; P.max_xa_alt = so->max_XA_hits_alt;
     int32_t *d_sel = (int32_t *)c->b_cg_out.p;
-    if (n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits, (size_t)n_hits * sizeof(bm2h_cg_mark)))) return rc;
-    if ((rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
+    if (!d_hits && n_hits && (rc = bm2_copy_h2d(c, (void *)P.hits, hits, (size_t)n_hits * sizeof(bm2h_cg_mark)))) return rc;
+    if (!d_off && (rc = bm2_copy_h2d(c, (void *)P.hit_off, hoff.data(), (size_t)(n_lists + 1) * 8))) return rc;
     if (plans && n_units && (rc = bm2_copy_h2d(c, (void *)P.plans, plans, (size_t)n_units * sizeof(bm2_pairplan_t)))) return rc;
     if (n_heavy) {
         if ((rc = bm2_copy_h2d(c, (void *)P.heavy_list, heavy_list.data(), (size_t)n_heavy * 4))) return rc;
@@ -276,6 +279,14 @@ int cgplan_run(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_op
     return BM2_OK;
 }
 }  // namespace
+
+// The selection of single-end lists whose 16 bytes a hit lie in HBM in decided order (semark.hip calls this between its kernels and its
+// download): d_hits[k] = hit h_off[0] + k, d_off = the offsets from 0 on the device, h_off their host copy in the caller's numbering, which
+// sel speaks.  See cgplan_run.
+int bm2h_cgplan_resident(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2h_cg_mark *d_hits,
+                         const int64_t *d_off, const int64_t *h_off, int32_t *sel, int64_t cap, int64_t *n_out, int64_t *heavy, int64_t first_list) {
+    return cgplan_run(c, who, opt, so, n_lists, nullptr, h_off, nullptr, sel, cap, n_out, heavy, first_list, d_hits, d_off);
+}
 
 extern "C" int bm2_cigar_plan_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2_alnreg_t *hits,
                                   const int64_t *hit_off, const bm2_pairplan_t *plans, int32_t *sel, int64_t cap, int64_t *n_out) {

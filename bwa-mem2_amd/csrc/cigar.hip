@@ -604,5 +604,6 @@ extern "C" int bm2_sam_se_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     if (!c || !c->has_index || !c->ix.ref_string) { bm2_set_error("bm2_sam_se_dev: the context holds no index"); return BM2_EINVAL; }
     bm2h_text_scope text(&c, 1);
     bm2h_cgplan_scope cgplan(&c, 1);
+    bm2h_semark_scope semark(&c, 1);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, bm2_dev_cigar_batch, c);
 }

@@ -187,6 +187,30 @@ struct bm2h_cgplan_scope : bm2h_ctx_scope {
     bm2h_cgplan_hook hook;
     bm2h_cgplan_scope(bm2_ctx *const *ctx, int n);
 };
+// cgplan.hip's kernels on single-end lists whose packed hits lie in HBM in decided order (semark.hip's kernels left them): d_hits[k] = hit
+// h_off[0] + k, d_off = the n_lists + 1 offsets from 0 on the device, h_off = their host copy in the caller's numbering, which sel speaks.
+// Nothing is uploaded but the heavy list.  *heavy = lists that took the wavefront form; first_list names a list in a message.
+int bm2h_cgplan_resident(bm2_ctx *c, const char *who, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, const bm2h_cg_mark *d_hits,
+                         const int64_t *d_off, const int64_t *h_off, int32_t *sel, int64_t cap, int64_t *n_out, int64_t *heavy, int64_t first_list);
+// The `decide` phase of the single-end tail for one chunk (bm2_se_mark_dev's arguments after the context), and with n_out != NULL the CIGAR
+// plan of the marked lists as well (sel, cap, *n_out as for bm2h_cgplan_batch_fn; sel speaks hit_off's numbering AFTER the lists have been
+// reordered).  Set through bm2h_semark_hook for the calling thread; when it is set AND so->flag has BM2_SAM_F_DEVICE_SEMARK, the CIGAR session
+// of bm2h_sam_se marks no read on its threads: it calls the hook once on alnregs / reg_off / n_processed -- with n_out when
+// BM2_SAM_F_DEVICE_CGPLAN is set too, and then packs nothing either.  0 = success.
+typedef int (*bm2h_semark_batch_fn)(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, bm2_alnreg_t *hits, const int64_t *hit_off,
+                                    int64_t first_id, int32_t *n_pri, int32_t *sel, int64_t cap, int64_t *n_out);
+struct bm2h_semark_hook {
+    bm2h_semark_hook(bm2h_semark_batch_fn fn, void *user);
+    ~bm2h_semark_hook();
+};
+// The device's hook (semark.hip; user = bm2h_text_ctxs: the lists cut into contiguous parts, knob BM2_SEMARK_PART, one context and host
+// thread per part, part g's ids from first_id + its first list, the parts' selections appended in order) and its scope.
+int bm2h_dev_semark_batch(void *user, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, bm2_alnreg_t *hits, const int64_t *hit_off,
+                          int64_t first_id, int32_t *n_pri, int32_t *sel, int64_t cap, int64_t *n_out);
+struct bm2h_semark_scope : bm2h_ctx_scope {
+    bm2h_semark_hook hook;
+    bm2h_semark_scope(bm2_ctx *const *ctx, int n);
+};
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,

@@ -286,5 +286,6 @@ extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     bm2h_text_ctxs m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
     bm2h_cgplan_scope cgplan(ctxs, n_ctx);
+    bm2h_semark_scope semark(ctxs, n_ctx);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, multi_cigar_batch, &m);
 }

@@ -365,7 +365,9 @@ thread_local bm2h_pestat_batch_fn t_pestat_fn = nullptr;        // the calling t
 thread_local void *t_pestat_user = nullptr;
 thread_local bm2h_cgplan_batch_fn t_cgplan_fn = nullptr;        // the calling thread's hook (bm2h_cgplan_hook)
 thread_local void *t_cgplan_user = nullptr;
-thread_local uint64_t t_tail_epoch = 0;                          // bm2h_tail_epoch()
+thread_local bm2h_semark_batch_fn t_semark_fn = nullptr;        // the calling thread's hook (bm2h_semark_hook)
+thread_local void *t_semark_user = nullptr;
+thread_local uint64_t t_tail_epoch = 0;                         // bm2h_tail_epoch()
 std::atomic<uint64_t> g_tail_epoch{0};
 
 // the band of the first try (bwamem.cpp:1743-1747) and the retry loop (:1748-1766) of mem_reg2aln around bwa_gen_cigar2
@@ -1734,6 +1736,8 @@ bm2h_pestat_hook::bm2h_pestat_hook(bm2h_pestat_batch_fn fn, void *user) { t_pest
 bm2h_pestat_hook::~bm2h_pestat_hook() { t_pestat_fn = nullptr; t_pestat_user = nullptr; }
 bm2h_cgplan_hook::bm2h_cgplan_hook(bm2h_cgplan_batch_fn fn, void *user) { t_cgplan_fn = fn; t_cgplan_user = user; }
 bm2h_cgplan_hook::~bm2h_cgplan_hook() { t_cgplan_fn = nullptr; t_cgplan_user = nullptr; }
+bm2h_semark_hook::bm2h_semark_hook(bm2h_semark_batch_fn fn, void *user) { t_semark_fn = fn; t_semark_user = user; }
+bm2h_semark_hook::~bm2h_semark_hook() { t_semark_fn = nullptr; t_semark_user = nullptr; }
 uint64_t bm2h_tail_epoch() { return t_tail_epoch; }
 
 static std::atomic<long long> g_cp_lists{0}, g_cp_hits{0}, g_cp_sel{0}, g_cp_heavy{0};
@@ -1827,6 +1831,33 @@ extern "C" int bm2_cigar_plan(const bm2_opt *opt, const bm2_sam_opt *so, int32_t
     }
     *n_out = got;
     if (got > cap) { bm2_set_error("bm2_cigar_plan: %lld hits are selected, room for %lld", (long long)got, (long long)cap); return BM2_ECAP; }
+    return BM2_OK;
+}
+
+// The `decide` phase of the single-end tail for a batch of lists (bm2h_sam_se's decide lambda behind a C name): the host form, and the
+// oracle of semark.hip.
+extern "C" int bm2_se_mark(const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, bm2_alnreg_t *hits, const int64_t *hit_off, int64_t first_id,
+                           int32_t *n_pri) {
+    if (!opt || !so || n_lists < 0 || !hit_off) { bm2_set_error("bm2_se_mark: bad argument"); return BM2_EINVAL; }
+    int rc = bm2h_check_list_off("bm2_se_mark", n_lists, hit_off);
+    if (rc) return rc;
+    if (hit_off[n_lists] > hit_off[0] && !hits) { bm2_set_error("bm2_se_mark: bad argument"); return BM2_EINVAL; }
+    int nt = so->n_threads > 0 ? so->n_threads : bm2_effective_cpus();
+    const int blk = 512, n_blk = (n_lists + blk - 1) / blk;
+    if (nt > n_blk) nt = n_blk;
+    if (nt < 1) nt = 1;
+    std::atomic<int> next(0);
+    run_threads(nt, [&]() {
+        for (int b; (b = next.fetch_add(1)) < n_blk;)
+            for (int i = b * blk; i < n_lists && i < (b + 1) * blk; ++i) {
+                t_scratch.reset();
+                bm2_alnreg_t *a = hits + hit_off[i];
+                const int n = (int)(hit_off[i + 1] - hit_off[i]);
+                const int pri = mark_primary_se(opt, n, a, first_id + i);
+                if (so->flag & F_PRIMARY5) reorder_primary5(so->T, n, a);
+                if (n_pri) n_pri[i] = pri;
+            }
+    });
     return BM2_OK;
 }
 
@@ -2269,6 +2300,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     }
     if ((so->flag & BM2_SAM_F_DEVICE_PESTAT) && !t_pestat_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PESTAT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
+    if (so->flag & BM2_SAM_F_DEVICE_SEMARK) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_SEMARK is a flag of the single-end tail (bm2_sam_se_dev)"); return BM2_EINVAL; }
     const bool dev_cgplan = (so->flag & BM2_SAM_F_DEVICE_CGPLAN) != 0;
     const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0, dev_plan = (so->flag & BM2_SAM_F_DEVICE_PLAN) != 0;
     const bool dev_pestat = (so->flag & BM2_SAM_F_DEVICE_PESTAT) != 0 && !pes_in;       // (a model that is given leaves nothing to compute)
@@ -2774,6 +2806,8 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (so->flag & BM2_SAM_F_DEVICE_PLAN) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PLAN is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_PESTAT) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PESTAT is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_SEMARK) && (!t_semark_fn || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_SEMARK needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
+    const bool dev_semark = (so->flag & BM2_SAM_F_DEVICE_SEMARK) != 0;
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };
     struct Budget { int was; explicit Budget(int n) : was(bm2_host_thread_budget()) { bm2_host_thread_budget() = n; } ~Budget() { bm2_host_thread_budget() = was; } } budget(so->n_threads);
@@ -2803,15 +2837,20 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
         std::atomic<int> next(0);
         if (so->flag & BM2_SAM_F_DEVICE_CGPLAN) {                // no dry emit: decide, pack the 16 bytes a hit the rule reads, one call of the hook
             TailProf prof("sam_se");
-            run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
-                for (int b; (b = next.fetch_add(1)) < n_blk;)
-                    for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) decide(i);
-            });
-            prof.mark("decide");
             const int64_t hb = reg_off[0], tot = reg_off[n_reads] - hb;
-            std::vector<bm2h_cg_mark> packed((size_t)tot + 1);
             std::vector<int32_t> sel((size_t)tot + 1);
-            {
+            int64_t got = 0;
+            if (dev_semark) {                                    // BM2_SAM_F_DEVICE_SEMARK as well: the lists marked and their batch picked in one call, nothing packed here
+                const int rc = t_semark_fn(t_semark_user, opt, so, n_reads, alnregs, reg_off, n_processed, nullptr, sel.data(), tot, &got);
+                if (rc) return rc;
+                prof.mark("decide (device)");
+            } else {
+                run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
+                    for (int b; (b = next.fetch_add(1)) < n_blk;)
+                        for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) decide(i);
+                });
+                prof.mark("decide");
+                std::vector<bm2h_cg_mark> packed((size_t)tot + 1);
                 std::atomic<int64_t> nx(0);
                 run_threads(n_threads < tot / 65536 + 1 ? n_threads : (int)(tot / 65536 + 1), [&]() {
                     for (int64_t lo; (lo = nx.fetch_add(65536)) < tot;)
@@ -2820,21 +2859,26 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
                             d.score = a.score; d.secondary = a.secondary; d.secondary_all = a.secondary_all; d.is_alt = a.is_alt;
                         }
                 });
+                const int rc = t_cgplan_fn(t_cgplan_user, opt, so, n_reads, packed.data(), reg_off, nullptr, sel.data(), tot, &got);
+                if (rc) return rc;
             }
-            int64_t got = 0;
-            const int rc = t_cgplan_fn(t_cgplan_user, opt, so, n_reads, packed.data(), reg_off, nullptr, sel.data(), tot, &got);
-            if (rc) return rc;
             recs.resize(1);
             recs[0].reserve((size_t)got);
             for (int64_t k = 0; k < got; ++k) { const int32_t pad = alnregs[sel[(size_t)k]].pad; if (pad > 0) recs[0].push_back(pad - 1); }
             prof.mark("cigar plan (device)");
         } else {
+            if (dev_semark) {                                    // the lists marked in one call; the dry pass below emits only
+                TailProf prof("sam_se");
+                const int rc = t_semark_fn(t_semark_user, opt, so, n_reads, alnregs, reg_off, n_processed, nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+                prof.mark("decide (device)");
+            }
             run_threads(n_threads < n_blk ? n_threads : n_blk, [&]() {
                 Text sink;
                 for (int b; (b = next.fetch_add(1)) < n_blk;) {
                     t_cg.mode = 1; t_cg.rec = &recs[(size_t)b];
                     for (int i = b * blk; i < n_reads && i < (b + 1) * blk; ++i) {
-                        decide(i);
+                        if (!dev_semark) decide(i);
                         emit(i, sink);
                         sink.clear();
                     }

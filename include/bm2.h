@@ -506,6 +506,29 @@ int bm2_cigar_plan_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, in
  * (single-end) or pairs that took the wavefront form (more than 16 hits). */
 void bm2_sam_cigar_plan_stats(int64_t *lists, int64_t *hits, int64_t *selected, int64_t *lists_heavy);
 
+/* ---- the `decide` phase of the single-end tail for a batch of hit lists (semark.hip): which hits of a read are primary.  List i is
+ * hits[hit_off[i], hit_off[i + 1]), n_lists + 1 offsets, checked (non-negative, non-decreasing: BM2_EINVAL) before anything follows one;
+ * hit_off[0] need not be 0.  The id of list i is first_id + i: it seeds hash_64(id + k) of hit k, the tie-break of both rankings, as
+ * bm2_sam_se does with n_processed + i.  Per list: mem_mark_primary_se (bwamem.cpp:1392-1465), then mem_reorder_primary5 (:1496-1519)
+ * with so->T when so->flag has MEM_F_PRIMARY5.  The hits are reordered and annotated IN PLACE: sub, alt_sc, secondary, secondary_all and
+ * hash are set, sub_n is incremented (not reset), and every other field travels with its hit, pad included.  n_pri[i] = the hits of
+ * list i on the primary assembly (not on an ALT contig); n_pri may be NULL.  n_lists == 0 is a success that touches nothing.
+ * bm2_se_mark is the host code of bm2_sam_se's decide step behind a C name, and the oracle; bm2_se_mark_dev reads nothing of an index (a
+ * context created without one will do) and marks EVERY list on the device, whatever its length: 20 B a hit go up, 32 B a hit come down. */
+int bm2_se_mark(const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, bm2_alnreg_t *hits, const int64_t *hit_off, int64_t first_id,
+                int32_t *n_pri);
+int bm2_se_mark_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32_t n_lists, bm2_alnreg_t *hits, const int64_t *hit_off,
+                    int64_t first_id, int32_t *n_pri);
+/* A library-private bit of bm2_sam_opt.flag, alone or with BM2_SAM_F_DEVICE_CGPLAN and / or BM2_SAM_F_DEVICE_TEXT: the CIGAR session of
+ * bm2_sam_se_dev and bm2_sam_se_dev_multi marks no read on the host threads; the chunk's lists go through bm2_se_mark_dev's kernels on
+ * their context(s) in one call.  With BM2_SAM_F_DEVICE_CGPLAN as well the marked lists stay on the device, the plan's kernels read them
+ * there, and the host packs nothing for the plan.  Same bytes, same bm2_sam_cigar_stats.  Off by default.  bm2_sam_se has no context and
+ * answers BM2_EINVAL to it; so do bm2_sam_pe and its _dev forms (a flag of the single-end tail). */
+#define BM2_SAM_F_DEVICE_SEMARK 0x40000000
+/* of the last bm2_se_mark_dev call on this process, or of the last tail with the bit: lists, hits, and the lists that took the
+ * wavefront form (more than 16 hits). */
+void bm2_sam_se_mark_stats(int64_t *lists, int64_t *hits, int64_t *lists_heavy);
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

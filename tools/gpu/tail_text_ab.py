@@ -19,6 +19,10 @@ phases to read: `sam_pe: pestat` against `sam_pe: pestat (device)`, and `pe_plan
 --bit cgplan|all+cgplan: BM2_SAM_F_DEVICE_CGPLAN (the CIGAR batch picked by bm2_cigar_plan_dev's kernels, no dry emit pass) alone and with
 the five other bits; the result holds bm2_sam_cigar_plan_stats and the bytes the plan moves.  The phases to read: `sam_pe: decide + dry
 emit` against `sam_pe: decide` + `sam_pe: cigar plan (device)`, and `cigar_session: batch list`.
+--bit semark|semark+cgplan (these imply --single-end): BM2_SAM_F_DEVICE_SEMARK (the single-end tail's primary hits marked by
+bm2_se_mark_dev's kernels, one call a chunk) alone and with the CIGAR plan reading the marked lists where they lie; the result holds
+bm2_sam_se_mark_stats and the bytes the marking moves.  The phases to read: `sam_se: decide` against `sam_se: decide (device)`.
+--single-end: the two files of the chunk as ONE single-end input of 2 x --pairs reads through bm2_sam_se_dev (any bit the single-end tail takes).
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
 import json
@@ -110,13 +114,16 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan", "cgplan", "all+cgplan"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan", "cgplan", "all+cgplan", "semark", "semark+cgplan"))
+    ap.add_argument("--single-end", action="store_true")
     a = ap.parse_args()
+    if "semark" in a.bit:
+        a.single_end = True
     res = {}
     if a.parent_lib:                                             # the baseline first, in a process of its own
         tmp = a.out + ".parent.json"
         subprocess.check_call([sys.executable, os.path.abspath(__file__), "--out", tmp, "--lib", a.parent_lib, "--variants", "off", "--pairs", str(a.pairs),
-                               "--genome-mbp", str(a.genome_mbp), "--workdir", a.workdir, "--calls", str(a.calls), "--threads", str(a.threads)])
+                               "--genome-mbp", str(a.genome_mbp), "--workdir", a.workdir, "--calls", str(a.calls), "--threads", str(a.threads)] + (["--single-end"] if a.single_end else []))
         res["parent"] = json.load(open(tmp))
         os.remove(tmp)
     import bench
@@ -131,32 +138,33 @@ def main():
     os.remove(fa); os.remove(fb)
     ctx = bm2.Context(0, prefix)
     opt = bm2.default_opt()
-    ch = bm2.FastqChunk(t1, t2, 16)
+    ch = bm2.FastqChunk(t1 + t2, None, 16) if a.single_end else bm2.FastqChunk(t1, t2, 16)
+    paired = not a.single_end
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
     on = set({"both": "text+decide", "all": "text+decide+rescue", "all+cgplan": "text+decide+rescue+plan+pestat+cgplan"}.get(a.bit, a.bit).split("+"))
     bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if "text" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if "decide" in on else 0) | \
            (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PESTAT", 0) if "pestat" in on else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_CGPLAN", 0) if "cgplan" in on else 0)
+           (getattr(bm2, "SAM_F_DEVICE_CGPLAN", 0) if "cgplan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_SEMARK", 0) if "semark" in on else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
     if a.once:
-        txt = ctx.sam(ch, opt, so["on"], aln, aln_off, 0, True, out=bufs["on"].a)
+        txt = ctx.sam(ch, opt, so["on"], aln, aln_off, 0, paired, out=bufs["on"].a)
         print("[ab] one bit-on call: %d bytes, counters %s" % (len(txt), bm2.sam_text_stats()), file=sys.stderr)
         return
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided, rescued, planned_dev, model_dev, cgplan_dev = None, None, None, None, None, None, None
+    counters, first, decided, rescued, planned_dev, model_dev, cgplan_dev, semark_dev = None, None, None, None, None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
         for v in variants:
             c0 = cpu_s(); t0 = time.perf_counter()
             with Stderr() as err:
-                txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, True, out=bufs[v].a)
+                txt = ctx.sam(ch, opt, so[v], aln, aln_off, 0, paired, out=bufs[v].a)
             dt, dc = time.perf_counter() - t0, cpu_s() - c0
             texts[v] = txt
             if v == "on" and "text" in on:
@@ -171,6 +179,8 @@ def main():
                 model_dev = bm2.sam_pestat_stats()
             if v == "on" and "cgplan" in on:
                 cgplan_dev = bm2.sam_cigar_plan_stats() + bm2.sam_cigar_stats()
+            if v == "on" and "semark" in on:
+                semark_dev = bm2.sam_se_mark_stats() + bm2.sam_cigar_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -178,7 +188,7 @@ def main():
         if first is None:
             first = texts[variants[0]].tobytes()
         print("[ab] call %d: %s" % (rep, {v: "%.1f ms" % (wall[v][-1] if wall[v] else 0.0) for v in variants}), file=sys.stderr, flush=True)
-    mine = {"reads": ch.n_reads, "text_bytes": len(first), "threads": a.threads, "lib": a.lib or "tree", "bit": a.bit, "variants": {}}
+    mine = {"reads": ch.n_reads, "single_end": bool(a.single_end), "text_bytes": len(first), "threads": a.threads, "lib": a.lib or "tree", "bit": a.bit, "variants": {}}
     for v in variants:
         keys = sorted(set(k for p in ph[v] for k in p))
         mine["variants"][v] = {"wall_ms": spread(wall[v]), "cpu_s": spread(cpu[v]),
@@ -212,6 +222,12 @@ def main():
         lists, hits, selected, heavy, planned, used, missed = cgplan_dev
         mine["cgplan_stats"] = {"lists": lists, "hits": hits, "selected": selected, "lists_heavy": heavy, "planned": planned, "used": used, "missed": missed}
         mine["cgplan_pcie"] = {"up": 16 * hits + 8 * (lists + 1) + 32 * (lists // 2), "down": 4 * selected + 12}
+        if "semark" in on:                                       # (the marked lists and their offsets lie on the device already: 12 B a heavy list go up)
+            mine["cgplan_pcie"]["up"] = 12 * heavy
+    if semark_dev is not None:                                   # (semark.hip: 20 B a hit and 8 B a list offset up; 32 B a hit down; with cgplan the 16 B a hit stay on the device)
+        lists, hits, heavy, planned, used, missed = semark_dev
+        mine["semark_stats"] = {"lists": lists, "hits": hits, "lists_heavy": heavy, "planned": planned, "used": used, "missed": missed}
+        mine["semark_pcie"] = {"up": 20 * hits + 8 * (lists + 1), "down": 32 * hits + 8, "cgplan_up_saved": 16 * hits if "cgplan" in on else 0}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

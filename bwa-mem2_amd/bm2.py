@@ -79,6 +79,16 @@ SAM_F_DEVICE_CGPLAN = 0x20000000    # BM2_SAM_F_DEVICE_CGPLAN: sam_se / sam_pe w
 SAM_F_DEVICE_SEMARK = 0x40000000    # BM2_SAM_F_DEVICE_SEMARK: sam_se with a context marks the primary hits of its lists with bm2_se_mark_dev, one call a chunk (off by default)
 
 
+SAM_F_DEVICE_CGPREP = 0x00800000    # BM2_SAM_F_DEVICE_CGPREP: sam_se / sam_pe with a context prepare their CIGAR batch (task slices, class order) with bm2_cigar_prep_dev (off by default)
+
+# bm2_cigar_hit_t (40 B), bm2_cigar_task_t (72 B), bm2_cigar_prep_t (56 B) of include/bm2.h
+CIGAR_HIT_DT = np.dtype([("rb", "<i8"), ("re", "<i8"), ("read", "<i4"), ("qb", "<i4"), ("qe", "<i4"), ("truesc", "<i4"), ("w", "<i4"), ("retry", "<i4")])
+CIGAR_TASK_DT = np.dtype([("q_off", "<i8"), ("rb", "<i8"), ("re", "<i8"), ("z_off", "<i8"), ("eh_off", "<i8"), ("cg_off", "<i8"), ("md_off", "<i8"),
+                          ("q_len", "<i4"), ("w", "<i4"), ("truesc", "<i4"), ("retry", "<i4")])
+CIGAR_PREP_DT = np.dtype([("z_bytes", "<i8"), ("eh_items", "<i8"), ("cg_items", "<i8"), ("md_bytes", "<i8"), ("n_shape", "<i4", (4,)), ("qmax", "<i4"), ("pad", "<i4")])
+assert (CIGAR_HIT_DT.itemsize, CIGAR_TASK_DT.itemsize, CIGAR_PREP_DT.itemsize) == (40, 72, 56)
+
+
 class KswResult(C.Structure):       # bm2_ksw_result (include/bm2.h), 28 bytes
     _fields_ = [(n, C.c_int32) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
@@ -154,7 +164,8 @@ EXPORTS = ["bm2_index_load", "bm2_index_free", "bm2_opt_init", "bm2_opt_fill_scm
            "bm2_pe_rescue_plan_dev", "bm2_pe_rescue_queries", "bm2_pe_rescue_queries_dev", "bm2_sam_rescue_plan_stats",
            "bm2_pe_stat", "bm2_pe_stat_dev", "bm2_sam_pestat_stats",
            "bm2_cigar_plan", "bm2_cigar_plan_dev", "bm2_sam_cigar_plan_stats",
-           "bm2_se_mark", "bm2_se_mark_dev", "bm2_sam_se_mark_stats"]
+           "bm2_se_mark", "bm2_se_mark_dev", "bm2_sam_se_mark_stats",
+           "bm2_cigar_prep", "bm2_cigar_prep_dev", "bm2_sam_cigar_prep_stats"]
 
 _lib = None
 
@@ -540,6 +551,10 @@ class Context:
         """bm2_cigar_plan_dev: see cigar_plan()."""
         return cigar_plan(opt, sam_opt, hits, hit_off, plans, ctx=self, cap=cap)
 
+    def cigar_prep(self, opt, l_pac, off, ln, hits):
+        """bm2_cigar_prep_dev: see cigar_prep()."""
+        return cigar_prep(opt, l_pac, off, ln, hits, ctx=self)
+
     def se_mark(self, opt, sam_opt, hits, hit_off, first_id=0):
         """bm2_se_mark_dev: see se_mark()."""
         return se_mark(opt, sam_opt, hits, hit_off, first_id, ctx=self)
@@ -846,6 +861,39 @@ def cigar_plan(opt, sam_opt, hits, hit_off, plans=None, ctx=None, cap=None):
         return rc, sel[:room], n_out.value
     _chk(rc, who)
     return sel[:n_out.value].copy()
+
+
+def sam_cigar_prep_stats():
+    """(tasks, (ring, row, global, flat), bytes_up, host_fallbacks) of the last device preparation of a CIGAR batch (Context.cigar_prep, or a
+    tail with SAM_F_DEVICE_CGPREP, summed over its contexts)"""
+    t, up, fb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    sh = (C.c_int64 * 4)()
+    L = lib()
+    L.bm2_sam_cigar_prep_stats.restype = None
+    L.bm2_sam_cigar_prep_stats(C.byref(t), sh, C.byref(up), C.byref(fb))
+    return t.value, tuple(int(v) for v in sh), up.value, fb.value
+
+
+def cigar_prep(opt, l_pac, off, ln, hits, ctx=None):
+    """The CIGAR batch of `hits` (CIGAR_HIT_DT) prepared for cigar.hip's kernels (bm2_cigar_prep; with ctx = a Context, with or without an
+    index: bm2_cigar_prep_dev, the same on the device).  off / ln: the reads' offsets and lengths (their codes are not read).
+    -> (tasks CIGAR_TASK_DT, order int32, tot: one CIGAR_PREP_DT record)."""
+    L = lib()
+    hits = np.ascontiguousarray(hits, CIGAR_HIT_DT)
+    off = np.ascontiguousarray(off, np.int64)
+    ln = np.ascontiguousarray(ln, np.int32)
+    n = len(hits)
+    tasks = np.zeros(max(n, 1), CIGAR_TASK_DT)
+    order = np.full(max(n, 1), -1, np.int32)
+    tot = np.zeros(1, CIGAR_PREP_DT)
+    reads = Reads(len(ln), None, off.ctypes.data if len(off) else None, ln.ctypes.data if len(ln) else None)
+    args = (C.byref(opt), C.c_int64(l_pac), C.byref(reads), C.c_int32(n), C.c_void_p(hits.ctypes.data if n else None), C.c_void_p(tasks.ctypes.data),
+            C.c_void_p(order.ctypes.data), C.c_void_p(tot.ctypes.data))
+    if ctx is not None:
+        _chk(L.bm2_cigar_prep_dev(C.c_void_p(ctx.h), *args), "bm2_cigar_prep_dev")
+    else:
+        _chk(L.bm2_cigar_prep(*args), "bm2_cigar_prep")
+    return tasks[:n], order[:n], tot[0]
 
 
 def sam_se_mark_stats():

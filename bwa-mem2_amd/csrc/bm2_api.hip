@@ -528,6 +528,7 @@ extern "C" void bm2_destroy(bm2_ctx *c) {
     bm2_release(c->b_pl_in); bm2_release(c->b_pl_work); bm2_release(c->b_pl_out); bm2_release(c->b_pl_scan);
     bm2_release(c->b_cg_in); bm2_release(c->b_cg_work); bm2_release(c->b_cg_out); bm2_release(c->b_cg_scan);
     bm2_release(c->b_sm_in); bm2_release(c->b_sm_out); bm2_release(c->b_sm_work); bm2_release(c->b_sm_scan); bm2_release(c->b_sm_scan2);
+    bm2_release(c->b_cp_in); bm2_release(c->b_cp_work); bm2_release(c->b_cp_out); bm2_release(c->b_cp_scan);
     if (c->txt_pin) (void)hipHostFree(c->txt_pin);
     free_streams(c);
     delete c;

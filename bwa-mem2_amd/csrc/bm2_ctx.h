@@ -52,6 +52,11 @@ struct bm2_ctx {
     // workspaces of bm2_se_mark_dev (semark.hip): packed hits + offsets; results + n_pri + the 16 bytes a hit the CIGAR plan reads;
     // binning + the heavy list + the long lists' working records; two scans
     DevBuf b_sm_in, b_sm_out, b_sm_work, b_sm_scan, b_sm_scan2;
+    // workspaces of bm2_cigar_prep_dev (cgprep.hip): hits + the reads' offsets and lengths; sizes, keys, the four scans' offsets, block
+    // counts and their scan, totals; tasks + order of the record-level call; a scan.  None of them is one cigar_run carves its batch from.
+    DevBuf b_cp_in, b_cp_work, b_cp_out, b_cp_scan;
+    // set by bm2h_cgprep_scope for the SAM tail call in progress on this context: its CIGAR batch is prepared on the device
+    bool cgprep = false;
     // What b_pl_in holds since the model's pass of the SAM tail call in progress (pestat.hip), in plan_run's layout: the hits
     // [hbase, hbase + n_hits) of `hits` at 0 and the 2 * n_pairs + 1 re-based offsets of `hit_off` behind them.  epoch = that call's
     // number (bm2h_tail_epoch), 0 = nothing.  plan_run sends neither again when its own arguments are these; whatever else writes

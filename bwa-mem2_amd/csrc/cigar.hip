@@ -20,43 +20,11 @@
 #define CG_MINUS_INF (-0x40000000)
 
 struct CigarPrm { int8_t mat[25]; int8_t pad[3]; int32_t o_del, e_del, o_ins, e_ins, a, w; int64_t l_pac; };
-struct CigarTask {
-    int64_t q_off, rb, re;
-    int64_t z_off, eh_off, cg_off, md_off;      // this task's slices of the scratch buffers
-    int32_t q_len, w, truesc, retry;            // retry = 1: w is the hit's band and the kernel runs mem_reg2aln's retry loop around the alignment
-};
+typedef bm2_cigar_task_t CigarTask;       // q_off, rb, re; z_off, eh_off, cg_off, md_off: this task's slices of the scratch buffers; q_len, w, truesc,
+                                          // retry = 1: w is the hit's band and the kernel runs mem_reg2aln's retry loop around the alignment
 struct CigarRes { int32_t score, nm, n_cigar, md_len; };
 
-// the band of ksw_global2 as bwa_gen_cigar2 sets it (bwa.cpp:289-301); host and device size and run with the same number
-static __host__ __device__ inline int cigar_band(int l_query, int rlen, int w_, int mat0, int o_del, int e_del, int o_ins, int e_ins) {
-    int max_ins = (int)((double)(((l_query + 1) >> 1) * mat0 - o_ins) / e_ins + 1.);
-    int max_del = (int)((double)(((l_query + 1) >> 1) * mat0 - o_del) / e_del + 1.);
-    int max_gap = max_ins > max_del ? max_ins : max_del;
-    max_gap = max_gap > 1 ? max_gap : 1;
-    const int dl = rlen > l_query ? rlen - l_query : l_query - rlen;
-    int w = (max_gap + dl + 1) >> 1;
-    w = w < w_ ? w : w_;
-    const int min_w = dl + 3;
-    return w > min_w ? w : min_w;
-}
-static __host__ __device__ inline bool cigar_range_ok(int64_t l_pac, int l_query, int64_t rb, int64_t re) {
-    if (l_query <= 0 || rb >= re || (rb < l_pac && re > l_pac)) return false;
-    return rb >= 0 && re <= (l_pac << 1);                       // bns_get_seq would clamp: a clamped range is the NULL return
-}
-// infer_bw, bwamem.cpp:1811-1818, and the band of mem_reg2aln's first try (:1743-1747)
-static __host__ __device__ inline int cigar_infer_bw(int l1, int l2, int score, int a, int q, int r) {
-    if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;
-    int w = (int)((double)((l1 < l2 ? l1 : l2) * a - score - q) / r + 2.);
-    const int d = l1 > l2 ? l1 - l2 : l2 - l1;
-    return w < d ? d : w;
-}
-static __host__ __device__ inline int cigar_first_band(int lq, int rlen, int truesc, int w_hit, int a, int w_opt, int o_del, int e_del, int o_ins, int e_ins) {
-    const int t = cigar_infer_bw(lq, rlen, truesc, a, o_del, e_del);
-    int w2 = cigar_infer_bw(lq, rlen, truesc, a, o_ins, e_ins);
-    w2 = w2 > t ? w2 : t;
-    if (w2 > w_opt) w2 = w2 < w_hit ? w2 : w_hit;
-    return w2;
-}
+// (the band of an alignment, the first band of a retried one and the range test: cigar_prep.h, shared with the batch's preparation)
 
 // kputw: plain decimal of v >= 0.  Digits by CONSTANT divisors, most significant first (the digit buffer of the obvious form -- fill backwards, copy
 // forwards -- is a local array under a run-time index: the compiler kept its twelve bytes in registers behind a select chain, ~60 VALU instructions per
@@ -87,9 +55,7 @@ static __device__ int put_dec(char *s, int n, int v) {
 // In the LDS shapes "minus infinity" is -22768 instead of -2^30 without changing a single comparison (every DP value is either a real
 // score or ONE sentinel plus an offset the reference has too; the two families never meet).  The query sits in LDS 4 bits per base.
 // Scores are computed, not looked up: (match, mismatch, ambiguous) = (mat[0], mat[1], mat[4]) -- the bwa_fill_scmat form the host checks.
-#define CG_SMALL 10000
-#define CG_MINF16 (-32768 + CG_SMALL)
-#define CG_RING 64
+#define CG_MINF16 (-32768 + CG_SMALL)      // (CG_SMALL, CG_RING: cigar_prep.h)
 enum { CG_GLOBAL = 0, CG_ROW = 1, CG_RINGED = 2 };
 enum { CG_NULL = -1, CG_DEFERRED = -3 };                          // CigarRes::n_cigar: the reference's NULL return; "try the next band in the ROW kernel"
 
@@ -357,109 +323,48 @@ k_cigar_compact(int n, const CigarTask *__restrict__ tasks, const CigarRes *__re
     else md_out[md_pos[i]] = 0;
 }
 
-// Runs the tasks (slices not yet assigned) against the context's resident reference; queries are ranges of `seqs` (uploaded here).
+// Runs a batch against the context's resident reference; queries are ranges of `seqs` (uploaded here).  The batch is either `tasks` (n of
+// them on the host, slices not yet assigned: prepared here on the host threads and uploaded with their order), or -- tasks == NULL --
+// the hits of `dev`, which go up as they lie and are prepared by cgprep.hip's kernels where the batch runs.  *refused is set when that
+// preparation answered BM2_EUNSUP (nothing has run: the caller may come again with host tasks).
 // Results: res[i] and the dense arrays (offsets cg_pos / md_pos have n + 1 entries).
-static int cigar_run(bm2_ctx *c, const bm2_opt *opt, std::vector<CigarTask> &tasks, const uint8_t *seqs, int64_t seq_bytes,
+struct CigarDevPrep { const bm2_reads *reads; const bm2h_cg_hit *hits; };
+static int cigar_run(bm2_ctx *c, const bm2_opt *opt, int n, CigarTask *tasks, const CigarDevPrep *dev, bool *refused, const uint8_t *seqs, int64_t seq_bytes,
                      std::vector<CigarRes> &h_res, std::vector<int64_t> &cg_pos, std::vector<int64_t> &md_pos, std::vector<uint32_t> &cg, std::vector<char> &md) {
     TailProf prof("gen_cigar_dev");
-    const int n = (int)tasks.size();
     int rc = bm2_check(hipSetDevice(c->device), "hipSetDevice");
     if (rc) return rc;
     CigarPrm prm; memset(&prm, 0, sizeof prm);
     for (int a = 0; a < 25; ++a) prm.mat[a] = opt->mat[a];
     prm.o_del = opt->o_del; prm.e_del = opt->e_del; prm.o_ins = opt->o_ins; prm.e_ins = opt->e_ins; prm.a = opt->a; prm.w = opt->w; prm.l_pac = c->ix.l_pac;
-    // slices of the scratch buffers (sized for the widest band a task can come to) and the cost class of every task: sizes per piece
-    // of the task list on the host's worker threads, offsets by a scan over the pieces, then the tasks' slices
-    static thread_local std::vector<int> order_tl; static thread_local std::vector<int64_t> cost_tl; static thread_local std::vector<int16_t> wb_tl;
-    std::vector<int> &order = order_tl; std::vector<int64_t> &cost = cost_tl; std::vector<int16_t> &wb1 = wb_tl;
-    if (order.size() < (size_t)n) { order.resize((size_t)n); cost.resize((size_t)n); wb1.resize((size_t)n); }
-    for (int i = 0; i < 5; i++) for (int j = 0; j < 5; j++) {       // the kernels compute scores from (match, mismatch, ambiguous), as the hot path does
-        const int want = (i == 4 || j == 4) ? opt->mat[4] : (i == j ? opt->mat[0] : opt->mat[1]);
-        if (opt->mat[i * 5 + j] != want) { bm2_set_error("bm2_gen_cigar_dev: scoring matrix is not of the bwa_fill_scmat form"); return BM2_EUNSUP; }
-    }
-    const int host_threads = bm2_host_threads();
-    const int64_t grain = 16384, pieces = ((int64_t)n + grain - 1) / grain;
-    struct Sz { int64_t z, e, c, m; int wb_first; };          // wb_first: the band of the first (or only) alignment, -1 = none (flat / NULL)
-    std::vector<Sz> at((size_t)pieces + 1, Sz{ 0, 0, 0, 0, -1 });
-    std::atomic<int> too_long(0);
-    auto sizes = [&](const CigarTask &T, Sz &s) {               // what the task takes of the four buffers; s.z = its DP area = its cost
-        s = Sz{ 0, 0, 0, 0, -1 };
-        if (!cigar_range_ok(prm.l_pac, T.q_len, T.rb, T.re)) return;
-        const int64_t rlen = T.re - T.rb;
-        if (rlen > 0x3fffffff) { too_long = 1; return; }
-        const int w_first = T.retry ? cigar_first_band(T.q_len, (int)rlen, T.truesc, T.w, prm.a, prm.w, prm.o_del, prm.e_del, prm.o_ins, prm.e_ins) : T.w;
-        if (!(T.q_len == rlen && w_first == 0)) {               // (a retried task never starts from band 0: the first score ends its loop)
-            const int w_cap = T.retry ? (w_first < prm.w << 2 ? prm.w << 2 : w_first) : T.w;
-            const int wb = cigar_band(T.q_len, (int)rlen, w_cap, prm.mat[0], prm.o_del, prm.e_del, prm.o_ins, prm.e_ins);
-            const int n_col = ((T.q_len < 2 * wb + 1 ? T.q_len : 2 * wb + 1) + 3) & ~3;      // a multiple of 4: every z slice starts 4-aligned
-            s.z = (int64_t)n_col * rlen; s.e = T.q_len + 1;
-            const int w0 = T.retry ? (w_first < prm.w << 2 ? w_first : prm.w << 2) : T.w;      // (the kernel's clamp of the first try)
-            s.wb_first = cigar_band(T.q_len, (int)rlen, w0, prm.mat[0], prm.o_del, prm.e_del, prm.o_ins, prm.e_ins);
-        }
-        s.c = T.q_len + rlen + 2; s.m = 2 * (T.q_len + rlen) + 16;
-    };
-    bm2_parallel_ranges(n, grain, host_threads, [&](int64_t lo, int64_t hi) {
-        Sz sum{ 0, 0, 0, 0, -1 }, s;
-        for (int64_t i = lo; i < hi; ++i) {
-            sizes(tasks[(size_t)i], s);
-            cost[(size_t)i] = s.z; wb1[(size_t)i] = (int16_t)(s.wb_first > 32000 ? 32000 : s.wb_first);
-            sum.z += s.z; sum.e += s.e; sum.c += s.c; sum.m += s.m;
-        }
-        at[(size_t)(lo / grain) + 1] = sum;
-    });
-    if (too_long.load()) { bm2_set_error("bm2_gen_cigar_dev: reference range too long"); return BM2_EINVAL; }
-    for (int64_t p = 0; p < pieces; ++p) { Sz &x = at[(size_t)p + 1]; const Sz &y = at[(size_t)p]; x.z += y.z; x.e += y.e; x.c += y.c; x.m += y.m; }
-    const int64_t zo = at[(size_t)pieces].z, eo = at[(size_t)pieces].e, co = at[(size_t)pieces].c, mo = at[(size_t)pieces].m;
-    bm2_parallel_ranges(n, grain, host_threads, [&](int64_t lo, int64_t hi) {
-        Sz o = at[(size_t)(lo / grain)], s;
-        for (int64_t i = lo; i < hi; ++i) {
-            CigarTask &T = tasks[(size_t)i];
-            T.z_off = o.z; T.eh_off = o.e; T.cg_off = o.c; T.md_off = o.m;
-            sizes(T, s);
-            o.z += s.z; o.e += s.e; o.c += s.c; o.m += s.m;
-        }
-    });
-    prof.mark("slices");
-    // lanes of a wavefront run their tasks side by side: neighbours should be of one shape (see k_gen_cigar) and cost alike.  Counting sort by
-    // (shape, cost on a log scale, expensive first); the order array is the four shapes' task lists one after the other.
-    enum { SH_RING = 0, SH_ROW = 1, SH_GLOBAL = 2, SH_FLAT = 3 };
-    int n_shape[4] = { 0, 0, 0, 0 }, qmax = 0;
-    {
-        int pen = 1;
-        for (int a = 0; a < 25; ++a) pen = std::max(pen, abs((int)opt->mat[a]));
-        pen = std::max(pen, std::max(opt->o_del + opt->e_del, opt->o_ins + opt->e_ins));
-        static const int no_lds = getenv("BM2_CIGAR_NO_LDS") ? atoi(getenv("BM2_CIGAR_NO_LDS")) : 0;
-        static const int no_ring = getenv("BM2_CIGAR_NO_RING") ? atoi(getenv("BM2_CIGAR_NO_RING")) : 0;
-        const int ring_by_band = bm2_knob("BM2_CIGAR_RING_BY_BAND", 1);
-        auto small = [&](int i) { const CigarTask &T = tasks[(size_t)i]; return !no_lds && T.q_len <= 220 && (int64_t)(T.q_len + (T.re - T.rb)) * pen < CG_SMALL; };
-        auto shape = [&](int i) {
-            if (cost[(size_t)i] == 0) return (int)SH_FLAT;       // (no DP area: the one-M case, or a NULL return)
-            if (!small(i)) return (int)SH_GLOBAL;
-            return (!no_ring && 2 * (int)wb1[(size_t)i] + 2 <= CG_RING) ? (int)SH_RING : (int)SH_ROW;
-        };
-        // (the RING tasks by the band of their FIRST try, exactly: a wavefront steps through the widest band among its 64 tasks, and `cost` -- the DP area
-        //  the task's slices are sized for, i.e. of the widest band its retry loop can come to -- is the same for nearly all of them)
-        auto cls = [&](int i) {
-            const int sh = shape(i);
-            if (sh == SH_RING && ring_by_band) return sh * 64 + 31 - std::min(std::max((int)wb1[(size_t)i], 0), 31);
-            const int64_t v = cost[(size_t)i]; const int k = v > 0 ? 64 - __builtin_clzll((unsigned long long)v) : 0; return sh * 64 + 63 - k;
-        };
-        bm2_counting_order(n, 256, host_threads, cls, order.data());
-        std::atomic<int> ns[4], qm(0);
-        for (auto &x : ns) x = 0;
-        bm2_parallel_ranges(n, grain, host_threads, [&](int64_t lo, int64_t hi) {
-            int c[4] = { 0, 0, 0, 0 }, q = 0;
-            for (int64_t i = lo; i < hi; ++i) { const int sh = shape((int)i); ++c[sh]; if (sh == SH_RING || sh == SH_ROW) q = std::max(q, tasks[(size_t)i].q_len); }
-            for (int k = 0; k < 4; ++k) ns[k] += c[k];
-            for (int cur = qm.load(); q > cur && !qm.compare_exchange_weak(cur, q);) {}
-        });
-        for (int k = 0; k < 4; ++k) n_shape[k] = ns[k].load();
-        qmax = qm.load();
-    }
-    prof.mark("order");
-    c->n_bsw = 0;                                               // (these scratch buffers held the resident S1 batch, if any: it is gone)
+    if (!cgp_scmat_ok(opt)) { bm2_set_error("bm2_gen_cigar_dev: scoring matrix is not of the bwa_fill_scmat form"); return BM2_EUNSUP; }
+    const CgpKnobs kn = bm2h_cigar_prep_knobs();
+    const CgpPrm P = cgp_prm(opt, c->ix.l_pac, kn.no_lds, kn.no_ring, kn.ring_by_band, tasks ? 0 : 1);
+    enum { SH_RING = CG_SH_RING, SH_ROW = CG_SH_ROW, SH_GLOBAL = CG_SH_GLOBAL, SH_FLAT = CG_SH_FLAT };
     DevBuf &b_seq = c->b_ref, &b_task = c->b_qer, &b_res = c->b_pairs, &b_scr = c->b_misc;
     const size_t task_bytes = ((size_t)n * sizeof(CigarTask) + 15) & ~(size_t)15, ord_bytes = ((size_t)n * sizeof(int) + 15) & ~(size_t)15;
+    bm2_cigar_prep_t tot;
+    static thread_local std::vector<int> order_tl;
+    std::vector<int> &order = order_tl;
+    if (tasks) {
+        if (order.size() < (size_t)n) order.resize((size_t)n);
+        if ((rc = bm2h_cigar_prep_tasks("bm2_gen_cigar_dev", P, n, tasks, order.data(), &tot, &prof))) return rc;      // (phases `slices` and `order`)
+    } else {
+        // (b_task is the one buffer of the batch the preparation writes: reserved before its kernels are given pointers into it; the
+        //  preparation's own workspaces are the context's b_cp_*, none of which this function carves)
+        c->n_bsw = 0;
+        if ((rc = bm2_reserve(b_task, task_bytes + ord_bytes + 64))) return rc;
+        int64_t up = 0;
+        rc = bm2h_cgprep_dev(c, "BM2_SAM_F_DEVICE_CGPREP", P, dev->reads, n, (const bm2_cigar_hit_t *)dev->hits, nullptr, (CigarTask *)b_task.p,
+                             (int32_t *)((char *)b_task.p + task_bytes), &tot, &up);
+        if (rc == BM2_EUNSUP && refused) *refused = true;
+        if (rc) return rc;
+        bm2h_cgprep_stats_add(&tot, up, 0);
+        prof.mark("prep (device)");
+    }
+    const int64_t zo = tot.z_bytes, eo = tot.eh_items, co = tot.cg_items, mo = tot.md_bytes;
+    const int *n_shape = tot.n_shape; const int qmax = tot.qmax;
+    c->n_bsw = 0;                                               // (these scratch buffers held the resident S1 batch, if any: it is gone)
     const size_t z_bytes = ((size_t)zo + 15) & ~(size_t)15, eh_bytes = (size_t)eo * sizeof(int2), cg_bytes = ((size_t)co * 4 + 15) & ~(size_t)15, md_bytes = ((size_t)mo + 15) & ~(size_t)15;
     const size_t res_bytes = ((size_t)n * sizeof(CigarRes) + 15) & ~(size_t)15, cnt_bytes = ((size_t)(n + 2) * 4 + 15) & ~(size_t)15, pos_bytes = (size_t)(n + 2) * 8;
     const size_t defer_bytes = ((size_t)(n_shape[SH_RING] + 4) * 4 + 15) & ~(size_t)15;      // [0] = count, then the list
@@ -477,8 +382,8 @@ static int cigar_run(bm2_ctx *c, const bm2_opt *opt, std::vector<CigarTask> &tas
     uint32_t *d_cg = (uint32_t *)((char *)d_eh + eh_bytes); char *d_md = (char *)d_cg + cg_bytes;
     prof.mark("reserve");
     rc = bm2_copy_h2d(c, b_seq.p, seqs, (size_t)seq_bytes);        // (pageable memory: through the context's pinned staging buffers)
-    if (!rc) rc = bm2_copy_h2d(c, d_task, tasks.data(), (size_t)n * sizeof(CigarTask));
-    if (!rc) rc = bm2_copy_h2d(c, d_order, order.data(), (size_t)n * sizeof(int));
+    if (!rc && tasks) rc = bm2_copy_h2d(c, d_task, tasks, (size_t)n * sizeof(CigarTask));
+    if (!rc && tasks) rc = bm2_copy_h2d(c, d_order, order.data(), (size_t)n * sizeof(int));
     if (rc) return rc;
     const size_t lds_q = (size_t)((qmax + 7) / 8) * 256, lds_row = (size_t)(qmax + 1) * 256 + lds_q, lds_ring = (size_t)CG_RING * 256 + lds_q;
     if (lds_row > 64 * 1024 && (rc = bm2_check(hipFuncSetAttribute((const void *)k_gen_cigar<CG_ROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row), "hipFuncSetAttribute(k_gen_cigar)"))) return rc;
@@ -555,7 +460,7 @@ extern "C" int bm2_gen_cigar_dev(bm2_ctx *c, const bm2_opt *opt, int32_t n, cons
         T.q_off = q_off[i]; T.q_len = q_len[i]; T.rb = rb[i]; T.re = re[i]; T.w = w[i];
     }
     std::vector<CigarRes> res; std::vector<int64_t> cg_pos, md_pos; std::vector<uint32_t> cg; std::vector<char> mdv;
-    const int rc = cigar_run(c, opt, tasks, seqs, seq_bytes, res, cg_pos, md_pos, cg, mdv);
+    const int rc = cigar_run(c, opt, n, tasks.data(), nullptr, nullptr, seqs, seq_bytes, res, cg_pos, md_pos, cg, mdv);
     if (rc) return rc;
     int64_t oc = 0, om = 0;                                     // the caller's layout: NULL results take no space at all
     for (int i = 0; i < n; ++i) {
@@ -575,20 +480,28 @@ extern "C" int bm2_gen_cigar_dev(bm2_ctx *c, const bm2_opt *opt, int32_t n, cons
 // of mem_reg2aln run by the kernel, results compacted on the device.
 int bm2_dev_cigar_batch(void *user, const bm2_opt *opt, const bm2_reads *reads, int64_t enc_bytes, int32_t n, const bm2h_cg_hit *hits, bm2h_cg_out *out) {
     bm2_ctx *c = (bm2_ctx *)user;
-    static thread_local std::vector<CigarTask> tasks_tl;
-    std::vector<CigarTask> &tasks = tasks_tl;
-    tasks.resize((size_t)n);                                     // (cigar_run takes the list's size as the task count)
-    const int host_threads = bm2_host_threads();
-    bm2_parallel_ranges(n, 16384, host_threads, [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i) {
-            CigarTask &T = tasks[(size_t)i]; memset(&T, 0, sizeof T);
-            const bm2h_cg_hit &h = hits[i];
-            T.q_off = reads->off[h.read] + h.qb; T.q_len = h.qe - h.qb; T.rb = h.rb; T.re = h.re; T.w = h.w; T.truesc = h.truesc; T.retry = 1;
-        }
-    });
     static thread_local std::vector<CigarRes> res_tl;
     std::vector<CigarRes> &res = res_tl;
-    const int rc = cigar_run(c, opt, tasks, reads->enc, enc_bytes, res, out->cigar_off, out->md_off, out->cigar, out->md);
+    const int host_threads = bm2_host_threads();
+    int rc = BM2_EUNSUP; bool refused = false;
+    if (c->cgprep) {                                             // BM2_SAM_F_DEVICE_CGPREP: the hits go up as they lie, no task is made here
+        const CigarDevPrep dev = { reads, hits };
+        rc = cigar_run(c, opt, n, nullptr, &dev, &refused, reads->enc, enc_bytes, res, out->cigar_off, out->md_off, out->cigar, out->md);
+        if (refused) bm2h_cgprep_stats_add(nullptr, 0, 1);       // (prepared by the host path below, for this call)
+    }
+    if (!c->cgprep || refused) {
+        static thread_local std::vector<CigarTask> tasks_tl;
+        std::vector<CigarTask> &tasks = tasks_tl;
+        tasks.resize((size_t)n);
+        bm2_parallel_ranges(n, 16384, host_threads, [&](int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i) {
+                CigarTask &T = tasks[(size_t)i]; memset(&T, 0, sizeof T);
+                const bm2h_cg_hit &h = hits[i];
+                T.q_off = reads->off[h.read] + h.qb; T.q_len = h.qe - h.qb; T.rb = h.rb; T.re = h.re; T.w = h.w; T.truesc = h.truesc; T.retry = 1;
+            }
+        });
+        rc = cigar_run(c, opt, n, tasks.data(), nullptr, nullptr, reads->enc, enc_bytes, res, out->cigar_off, out->md_off, out->cigar, out->md);
+    }
     if (rc) return rc;
     c->tail_enc = reads->enc; c->tail_enc_bytes = (size_t)enc_bytes;       // (b_ref holds the reads' codes now: the text of the same call reads them there)
     out->score.resize((size_t)n); out->nm.resize((size_t)n); out->n_cigar.resize((size_t)n);
@@ -605,5 +518,6 @@ extern "C" int bm2_sam_se_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     bm2h_text_scope text(&c, 1);
     bm2h_cgplan_scope cgplan(&c, 1);
     bm2h_semark_scope semark(&c, 1);
+    bm2h_cgprep_scope cgprep(&c, 1, so);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, bm2_dev_cigar_batch, c);
 }

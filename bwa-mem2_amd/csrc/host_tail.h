@@ -211,6 +211,22 @@ struct bm2h_semark_scope : bm2h_ctx_scope {
     bm2h_semark_hook hook;
     bm2h_semark_scope(bm2_ctx *const *ctx, int n);
 };
+// The CIGAR batch prepared where it runs (BM2_SAM_F_DEVICE_CGPREP; cgprep.hip).  Unlike the hooks above this one is no function of the
+// calling thread: the CIGAR hook of the _multi forms runs every part of a batch on a host thread of its own, one context per part, so
+// the scope sets a field on each of its contexts (bm2_ctx::cgprep) for the duration of the call and bm2_dev_cigar_batch reads it from
+// the context it was given.  What the scope leaves with the calling thread is only the fact that contexts exist, for bm2h_sam_pe /
+// bm2h_sam_se to refuse the bit without one.
+struct bm2h_cgprep_mark {
+    explicit bm2h_cgprep_mark(bool on);
+    ~bm2h_cgprep_mark();
+};
+struct bm2h_cgprep_scope : bm2h_ctx_scope {
+    bm2h_cgprep_mark mark;
+    bm2h_cgprep_scope(bm2_ctx *const *ctx, int n, const bm2_sam_opt *so);
+    ~bm2h_cgprep_scope();
+};
+void bm2h_cgprep_stats_reset();
+void bm2h_cgprep_stats_add(const bm2_cigar_prep_t *tot, long long bytes_up, long long fallbacks);
 // bm2_sam_pe / bm2_sam_se with the rescue batch routed through `fn` and the CIGAR batch through `cfn` (NULL: host code in place)
 int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads, const bm2_read_text *txt,
                 const bm2_alnreg_t *alnregs, const int64_t *reg_off, int64_t n_processed, const bm2_pestat *pes_in, bm2_pestat *pes_out,
@@ -234,3 +250,18 @@ struct TailProf {
     }
     ~TailProf() { if (on) fprintf(stderr, "[tail] %-14s %-22s %8.1f ms\n", who, "TOTAL", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
 };
+
+// ---- the CIGAR batch's preparation (cigar_prep.h states the rule).  Host side, cigar_prep.cpp: the three launch knobs as the process
+// reads them; what both record-level forms refuse before they look at a task (who = the entry point; self = its context, or anything
+// non-NULL); and slices, order and totals of tasks whose q_off .. re and q_len .. retry are set (prof: the phases `slices` and `order`).
+// Device side, cgprep.hip: bm2h_cgprep_dev writes tasks and order of the batch into DEVICE memory (d_task, d_order: n entries each, not
+// in the b_cp_* workspaces) and brings the totals down, one synchronising copy.  hits: the host array, uploaded here -- or d_hits != NULL:
+// the hits lie in device memory already and nothing but the reads' offsets and lengths goes up.  *bytes_up = what went up.
+#include "cigar_prep.h"
+struct CgpKnobs { int no_lds, no_ring, ring_by_band; };
+CgpKnobs bm2h_cigar_prep_knobs();
+int bm2h_cigar_prep_args(const char *who, const void *self, const bm2_opt *opt, const bm2_reads *reads, int32_t n, const void *hits, const void *tasks,
+                         const void *order, const void *tot);
+int bm2h_cigar_prep_tasks(const char *who, const CgpPrm &P, int32_t n, bm2_cigar_task_t *tasks, int32_t *order, bm2_cigar_prep_t *tot, TailProf *prof);
+int bm2h_cgprep_dev(bm2_ctx *c, const char *who, const CgpPrm &P, const bm2_reads *reads, int32_t n, const bm2_cigar_hit_t *hits, const bm2_cigar_hit_t *d_hits,
+                    bm2_cigar_task_t *d_task, int32_t *d_order, bm2_cigar_prep_t *tot, int64_t *bytes_up);

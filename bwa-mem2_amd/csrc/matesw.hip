@@ -212,6 +212,7 @@ extern "C" int bm2_sam_pe_dev(bm2_ctx *c, const bm2_index_desc *idx, const bm2_o
     bm2h_plan_scope plan(&c, 1);
     bm2h_pestat_scope model(&c, 1);
     bm2h_cgplan_scope cgplan(&c, 1);
+    bm2h_cgprep_scope cgprep(&c, 1, so);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, dev_rescue_batch, c,
                        bm2_dev_cigar_batch, c);
 }
@@ -233,7 +234,7 @@ int multi_rescue_batch(void *user, int32_t n, const uint8_t *qbuf, int64_t qbuf_
 }
 int multi_cigar_batch(void *user, const bm2_opt *opt, const bm2_reads *reads, int64_t enc_bytes, int32_t n, const bm2h_cg_hit *hits, bm2h_cg_out *out) {
     const bm2h_text_ctxs *m = (const bm2h_text_ctxs *)user;
-    const int G = bm2_parts(n, 16384, m->n);
+    const int G = bm2_parts(n, bm2_knob("BM2_CIGAR_PART", 16384), m->n);       // knob: tasks that are worth a context of their own (launch policy)
     if (G <= 1) return bm2_dev_cigar_batch(m->ctx[0], opt, reads, enc_bytes, n, hits, out);
     std::vector<bm2h_cg_out> part((size_t)G);
     int rc = bm2_run_parts(G, bm2_part_budget(G), "context", [&](int g) {
@@ -277,6 +278,7 @@ extern "C" int bm2_sam_pe_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     bm2h_plan_scope plan(ctxs, n_ctx);
     bm2h_pestat_scope model(ctxs, n_ctx);
     bm2h_cgplan_scope cgplan(ctxs, n_ctx);
+    bm2h_cgprep_scope cgprep(ctxs, n_ctx, so);
     return bm2h_sam_pe(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, pes_in, pes_out, out, cap, n_out, multi_rescue_batch, &m, multi_cigar_batch, &m);
 }
 extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt *so, const bm2_reads *reads,
@@ -286,6 +288,7 @@ extern "C" int bm2_sam_se_dev_multi(bm2_ctx *const *ctxs, int n_ctx, const bm2_i
     bm2h_text_ctxs m = { ctxs, n_ctx };
     bm2h_text_scope text(ctxs, n_ctx);
     bm2h_cgplan_scope cgplan(ctxs, n_ctx);
+    bm2h_cgprep_scope cgprep(ctxs, n_ctx, so);
     bm2h_semark_scope semark(ctxs, n_ctx);
     return bm2h_sam_se(idx, opt, so, reads, txt, alnregs, reg_off, n_processed, out, cap, n_out, multi_cigar_batch, &m);
 }

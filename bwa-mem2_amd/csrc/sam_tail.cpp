@@ -367,6 +367,7 @@ thread_local bm2h_cgplan_batch_fn t_cgplan_fn = nullptr;        // the calling t
 thread_local void *t_cgplan_user = nullptr;
 thread_local bm2h_semark_batch_fn t_semark_fn = nullptr;        // the calling thread's hook (bm2h_semark_hook)
 thread_local void *t_semark_user = nullptr;
+thread_local bool t_cgprep_ctx = false;                          // the calling thread is inside a bm2h_cgprep_scope (contexts exist)
 thread_local uint64_t t_tail_epoch = 0;                         // bm2h_tail_epoch()
 std::atomic<uint64_t> g_tail_epoch{0};
 
@@ -1738,6 +1739,8 @@ bm2h_cgplan_hook::bm2h_cgplan_hook(bm2h_cgplan_batch_fn fn, void *user) { t_cgpl
 bm2h_cgplan_hook::~bm2h_cgplan_hook() { t_cgplan_fn = nullptr; t_cgplan_user = nullptr; }
 bm2h_semark_hook::bm2h_semark_hook(bm2h_semark_batch_fn fn, void *user) { t_semark_fn = fn; t_semark_user = user; }
 bm2h_semark_hook::~bm2h_semark_hook() { t_semark_fn = nullptr; t_semark_user = nullptr; }
+bm2h_cgprep_mark::bm2h_cgprep_mark(bool on) { t_cgprep_ctx = on; }
+bm2h_cgprep_mark::~bm2h_cgprep_mark() { t_cgprep_ctx = false; }
 uint64_t bm2h_tail_epoch() { return t_tail_epoch; }
 
 static std::atomic<long long> g_cp_lists{0}, g_cp_hits{0}, g_cp_sel{0}, g_cp_heavy{0};
@@ -2301,6 +2304,7 @@ int bm2h_sam_pe(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if ((so->flag & BM2_SAM_F_DEVICE_PESTAT) && !t_pestat_fn) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_PESTAT needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if (so->flag & BM2_SAM_F_DEVICE_SEMARK) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_SEMARK is a flag of the single-end tail (bm2_sam_se_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_CGPREP) && (!t_cgprep_ctx || !cfn)) { bm2_set_error("bm2_sam_pe: BM2_SAM_F_DEVICE_CGPREP needs a context (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     const bool dev_cgplan = (so->flag & BM2_SAM_F_DEVICE_CGPLAN) != 0;
     const bool dev_rescue = (so->flag & BM2_SAM_F_DEVICE_RESCUE) != 0, dev_plan = (so->flag & BM2_SAM_F_DEVICE_PLAN) != 0;
     const bool dev_pestat = (so->flag & BM2_SAM_F_DEVICE_PESTAT) != 0 && !pes_in;       // (a model that is given leaves nothing to compute)
@@ -2807,6 +2811,7 @@ int bm2h_sam_se(const bm2_index_desc *idx, const bm2_opt *opt, const bm2_sam_opt
     if (so->flag & BM2_SAM_F_DEVICE_PESTAT) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_PESTAT is a flag of the paired tail (bm2_sam_pe_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_CGPLAN) && (!t_cgplan_fn || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_CGPLAN needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     if ((so->flag & BM2_SAM_F_DEVICE_SEMARK) && (!t_semark_fn || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_SEMARK needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
+    if ((so->flag & BM2_SAM_F_DEVICE_CGPREP) && (!t_cgprep_ctx || !cfn)) { bm2_set_error("bm2_sam_se: BM2_SAM_F_DEVICE_CGPREP needs a context (bm2_sam_se_dev)"); return BM2_EINVAL; }
     const bool dev_semark = (so->flag & BM2_SAM_F_DEVICE_SEMARK) != 0;
     if (!idx->ref_string || !idx->ann_offset || !idx->ann_name) { bm2_set_error("bm2_sam_se: the index descriptor needs ref_string and contig names"); return BM2_EINVAL; }
     Ref R = { idx->l_pac, idx->ref_string, idx->n_seqs, idx->ann_offset, idx->ann_name, idx->ann_anno };

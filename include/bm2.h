@@ -529,6 +529,41 @@ int bm2_se_mark_dev(bm2_ctx *c, const bm2_opt *opt, const bm2_sam_opt *so, int32
  * wavefront form (more than 16 hits). */
 void bm2_sam_se_mark_stats(int64_t *lists, int64_t *hits, int64_t *lists_heavy);
 
+/* ---- the CIGAR batch of a chunk prepared for its kernels (cigar_prep.h states the rule; cgprep.hip is its device form): every hit
+ * becomes a task with its slices of the four scratch buffers (direction bytes, the global row of (H, E), CIGAR ops, MD bytes), and the
+ * batch is ordered by shape and cost class.  Of `reads` only n_reads, off and len are read (enc may be NULL); l_pac is an argument, so a
+ * context created without an index will do.  tasks[i] is task i: q_off = reads->off[read] + qb, q_len = qe - qb, and its four slices laid
+ * out in task order from 0 (every z_off a multiple of 4).  order = the tasks by class key, ascending, tasks of one key in ascending
+ * index; the keys run RING, ROW, GLOBAL, FLAT, the costliest class of a shape first.  tot = the four totals, the tasks of each shape
+ * and qmax, the longest q_len among RING and ROW tasks.  The launch knobs BM2_CIGAR_NO_LDS, BM2_CIGAR_NO_RING and
+ * BM2_CIGAR_RING_BY_BAND are read on the host by both forms.  n == 0 succeeds and touches nothing.  A NULL argument, n < 0, or a gap
+ * extension penalty <= 0 is BM2_EINVAL; a scoring matrix not of the bwa_fill_scmat form is BM2_EUNSUP; a `read` outside [0, n_reads) or
+ * 0 <= qb <= qe <= len[read] not holding is BM2_EINVAL naming the lowest offending task (detected, never followed); a valid reference
+ * range longer than 0x3fffffff is BM2_EINVAL.  bm2_cigar_prep is the host statement and the oracle.  bm2_cigar_prep_dev carries the
+ * per-task sizes as 32-bit values: a task one of whose slices reaches 2^31 (a DP area of 2^31 bytes) is BM2_EUNSUP there. */
+typedef struct { int64_t rb, re; int32_t read, qb, qe, truesc, w, retry; } bm2_cigar_hit_t;          /* 40 B; retry != 0: mem_reg2aln's retry loop runs around the alignment, w is the hit's band */
+typedef struct { int64_t q_off, rb, re, z_off, eh_off, cg_off, md_off;
+                 int32_t q_len, w, truesc, retry; } bm2_cigar_task_t;                               /* 72 B */
+typedef struct { int64_t z_bytes, eh_items, cg_items, md_bytes;
+                 int32_t n_shape[4]; int32_t qmax, pad; } bm2_cigar_prep_t;                         /* 56 B; n_shape in order RING, ROW, GLOBAL, FLAT */
+int bm2_cigar_prep    (const bm2_opt *opt, int64_t l_pac, const bm2_reads *reads, int32_t n, const bm2_cigar_hit_t *hits,
+                       bm2_cigar_task_t *tasks, int32_t *order, bm2_cigar_prep_t *tot);
+int bm2_cigar_prep_dev(bm2_ctx *c, const bm2_opt *opt, int64_t l_pac, const bm2_reads *reads, int32_t n, const bm2_cigar_hit_t *hits,
+                       bm2_cigar_task_t *tasks, int32_t *order, bm2_cigar_prep_t *tot);
+/* A library-private bit of bm2_sam_opt.flag (outside the reference's MEM_F_* range), alone or with any of the seven bits above, on
+ * single-end and paired runs: the CIGAR batch of bm2_sam_se_dev, bm2_sam_pe_dev and their _multi forms is prepared by
+ * bm2_cigar_prep_dev's kernels where it runs -- the 40-byte hits and the reads' offsets and lengths go up, the tasks and their order
+ * are written in device memory, 56 bytes of totals come down.  A batch the device form refuses with BM2_EUNSUP is prepared on the host
+ * for that call.  Same bytes, same bm2_sam_cigar_stats.  Off by default.  bm2_sam_se / bm2_sam_pe have no context and answer
+ * BM2_EINVAL to it. */
+#define BM2_SAM_F_DEVICE_CGPREP 0x00800000
+/* of the last bm2_cigar_prep_dev call on this process, or of the last tail with the bit (summed over its contexts): tasks, tasks by
+ * shape (RING, ROW, GLOBAL, FLAT), bytes uploaded for the prep, and batches prepared on the host after a refusal. */
+void bm2_sam_cigar_prep_stats(int64_t *tasks, int64_t shape[4], int64_t *bytes_up, int64_t *host_fallbacks);
+#ifdef __cplusplus
+static_assert(sizeof(bm2_cigar_hit_t) == 40 && sizeof(bm2_cigar_task_t) == 72 && sizeof(bm2_cigar_prep_t) == 56, "CIGAR prep records");
+#endif
+
 
 /* ---- the same path split so that a caller can keep inputs resident in HBM and time only the device work */
 int bm2_batch_upload(bm2_ctx *c, const bm2_reads *reads);                 /* H2D (pinned staging) */

@@ -103,6 +103,7 @@ void mem_process_seqs(mem_opt_t *opt, int64_t n_processed, int n, bseq1_t *seqs,
     { const char *dp = getenv("BM2_DEVICE_PLAN"); if (dp && dp[0] == '1' && (opt->flag & MEM_F_PE) && !(opt->flag & MEM_F_NO_RESCUE)) so.flag |= BM2_SAM_F_DEVICE_PLAN; }   // mate rescue planned, its queries made on the device (off by default)
     { const char *ds = getenv("BM2_DEVICE_PESTAT"); if (ds && ds[0] == '1' && (opt->flag & MEM_F_PE)) so.flag |= BM2_SAM_F_DEVICE_PESTAT; }   // the chunk's insert-size model counted on the device (off by default)
     { const char *dc = getenv("BM2_DEVICE_CGPLAN"); if (dc && dc[0] == '1') so.flag |= BM2_SAM_F_DEVICE_CGPLAN; }   // the CIGAR batch picked on the device, no dry emit pass (off by default)
+    { const char *dq = getenv("BM2_DEVICE_CGPREP"); if (dq && dq[0] == '1') so.flag |= BM2_SAM_F_DEVICE_CGPREP; }   // the CIGAR batch's task slices and class order made on the device (off by default)
     { const char *dm = getenv("BM2_DEVICE_SEMARK"); if (dm && dm[0] == '1' && !(opt->flag & MEM_F_PE)) so.flag |= BM2_SAM_F_DEVICE_SEMARK; }   // single-end: the primary hits marked on the device, one call a chunk (off by default; the paired tail refuses it)
     { const char *dd = getenv("BM2_DEVICE_DECIDE"); if (dd && dd[0] == '1' && (opt->flag & MEM_F_PE)) so.flag |= BM2_SAM_F_DEVICE_DECIDE; }   // the pairs' decisions made on the device (off by default; the single-end tail has none)
     // ---- reads: codes (the reference converts seqs[i].seq in place inside mem_kernel1_core; the strings stay untouched here)

@@ -33,7 +33,7 @@ def chunks(n_reads, lens, K, paired):
         lo = hi
 
 
-def run(prefix, fq, K=10000000, out_path="-", threads=0, hits_of=None, device_tail=False, contexts=1, device_text=False, device_decide=False, device_rescue=False, device_plan=False, device_pestat=False, device_cgplan=False, device_semark=False):
+def run(prefix, fq, K=10000000, out_path="-", threads=0, hits_of=None, device_tail=False, contexts=1, device_text=False, device_decide=False, device_rescue=False, device_plan=False, device_pestat=False, device_cgplan=False, device_semark=False, device_cgprep=False):
     """hits_of(enc, off, ln) -> (alnregs ALNREG_DT, aln_off): the device stage (up to and including mem_sort_dedup_patch); None = a
     Context on GPU 0.  contexts = G > 1: every chunk is split at multiples of 512 reads over G contexts -- one per GPU while there
     are GPUs, further ones share a replica -- and paired ONCE (bm2_chunk_hits_sharded): same SAM for every G.
@@ -50,9 +50,11 @@ def run(prefix, fq, K=10000000, out_path="-", threads=0, hits_of=None, device_ta
     device_cgplan (implies device_tail): the hits whose CIGARs the text asks for are picked on the device, without a dry emit pass
     (BM2_SAM_F_DEVICE_CGPLAN).
     device_semark (implies device_tail; single-end input): the primary hits of every chunk's lists are marked on the device in one call
-    (BM2_SAM_F_DEVICE_SEMARK)."""
+    (BM2_SAM_F_DEVICE_SEMARK).
+    device_cgprep (implies device_tail): the CIGAR batch is prepared -- task slices, class order -- by kernels where it runs, the hits go up
+    as they lie (BM2_SAM_F_DEVICE_CGPREP)."""
     import bm2
-    device_tail = device_tail or device_text or device_decide or device_rescue or device_plan or device_pestat or device_cgplan or device_semark
+    device_tail = device_tail or device_text or device_decide or device_rescue or device_plan or device_pestat or device_cgplan or device_semark or device_cgprep
     paired = len(fq) == 2
     if paired and device_semark:
         raise SystemExit("--device-semark is for single-end input")
@@ -72,7 +74,8 @@ def run(prefix, fq, K=10000000, out_path="-", threads=0, hits_of=None, device_ta
     lens = np.array([len(s) for s in seqs], np.int64)
     opt, so = bm2.default_opt(), bm2.default_sam_opt(n_threads=threads, flag=(bm2.SAM_F_DEVICE_TEXT if device_text else 0) | (bm2.SAM_F_DEVICE_DECIDE if device_decide else 0) |
                                            (bm2.SAM_F_DEVICE_RESCUE if device_rescue else 0) | (bm2.SAM_F_DEVICE_PLAN if device_plan else 0) | (bm2.SAM_F_DEVICE_PESTAT if device_pestat else 0) |
-                                           (bm2.SAM_F_DEVICE_CGPLAN if device_cgplan else 0) | (bm2.SAM_F_DEVICE_SEMARK if device_semark else 0))
+                                           (bm2.SAM_F_DEVICE_CGPLAN if device_cgplan else 0) | (bm2.SAM_F_DEVICE_SEMARK if device_semark else 0) |
+                                           (bm2.SAM_F_DEVICE_CGPREP if device_cgprep else 0))
     ctx = None
     if hits_of is None or device_tail:
         ctx = bm2.Context(0, prefix)
@@ -123,6 +126,7 @@ def main(argv=None):
     ap.add_argument("--device-plan", action="store_true", help="paired input: mate rescue planned and its queries made on the device too (implies --device-tail)")
     ap.add_argument("--device-pestat", action="store_true", help="paired input: every chunk's insert-size model counted on the device too (implies --device-tail)")
     ap.add_argument("--device-cgplan", action="store_true", help="the CIGAR batch picked on the device, no dry emit pass (implies --device-tail)")
+    ap.add_argument("--device-cgprep", action="store_true", help="the CIGAR batch's task slices and class order made on the device (implies --device-tail)")
     ap.add_argument("--device-semark", action="store_true", help="single-end input: the primary hits of every chunk marked on the device in one call (implies --device-tail)")
     ap.add_argument("--device-decide", action="store_true", help="paired input: the pairs' decisions made on the device too (implies --device-tail)")
     ap.add_argument("--contexts", type=int, default=1, help="split every chunk over this many contexts (GPUs first); one pairing per chunk")
@@ -130,7 +134,7 @@ def main(argv=None):
     ap.add_argument("prefix")
     ap.add_argument("fq", nargs="+")
     a = ap.parse_args(argv)
-    run(a.prefix, a.fq, a.K, a.o, a.threads, device_tail=a.device_tail, contexts=a.contexts, device_text=a.device_text, device_decide=a.device_decide, device_rescue=a.device_rescue, device_plan=a.device_plan, device_pestat=a.device_pestat, device_cgplan=a.device_cgplan, device_semark=a.device_semark)
+    run(a.prefix, a.fq, a.K, a.o, a.threads, device_tail=a.device_tail, contexts=a.contexts, device_text=a.device_text, device_decide=a.device_decide, device_rescue=a.device_rescue, device_plan=a.device_plan, device_pestat=a.device_pestat, device_cgplan=a.device_cgplan, device_semark=a.device_semark, device_cgprep=a.device_cgprep)
 
 
 if __name__ == "__main__":

@@ -22,6 +22,10 @@ emit` against `sam_pe: decide` + `sam_pe: cigar plan (device)`, and `cigar_sessi
 --bit semark|semark+cgplan (these imply --single-end): BM2_SAM_F_DEVICE_SEMARK (the single-end tail's primary hits marked by
 bm2_se_mark_dev's kernels, one call a chunk) alone and with the CIGAR plan reading the marked lists where they lie; the result holds
 bm2_sam_se_mark_stats and the bytes the marking moves.  The phases to read: `sam_se: decide` against `sam_se: decide (device)`.
+--bit cgprep|all+cgplan+cgprep|semark+cgplan+cgprep (the last implies --single-end): BM2_SAM_F_DEVICE_CGPREP (the CIGAR batch's task slices
+and class order made by bm2_cigar_prep_dev's kernels where the batch runs) alone and with every other bit of the paired / single-end tail;
+the result holds bm2_sam_cigar_prep_stats and the bytes the preparation moves.  The phases to read: `gen_cigar_dev: slices` +
+`gen_cigar_dev: order` against `gen_cigar_dev: prep (device)`.
 --single-end: the two files of the chunk as ONE single-end input of 2 x --pairs reads through bm2_sam_se_dev (any bit the single-end tail takes).
 --once: one bit-on call and nothing else (what a kernel trace of k_sam_size / k_sam_write is taken from)."""
 import argparse
@@ -114,7 +118,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan", "cgplan", "all+cgplan", "semark", "semark+cgplan"))
+    ap.add_argument("--bit", default="text", choices=("text", "decide", "both", "rescue", "rescue+decide", "all", "plan", "plan+rescue", "plan+rescue+decide+text", "pestat", "pestat+plan", "cgplan", "all+cgplan", "semark", "semark+cgplan", "cgprep", "all+cgplan+cgprep", "semark+cgplan+cgprep"))
     ap.add_argument("--single-end", action="store_true")
     a = ap.parse_args()
     if "semark" in a.bit:
@@ -143,10 +147,11 @@ def main():
     ctx.batch_upload_chunk(ch); ctx.batch_run(opt); ctx.batch_finish(opt)
     aln, aln_off = ctx.batch_download_alnregs()
     variants = a.variants.split(",")
-    on = set({"both": "text+decide", "all": "text+decide+rescue", "all+cgplan": "text+decide+rescue+plan+pestat+cgplan"}.get(a.bit, a.bit).split("+"))
+    on = set({"both": "text+decide", "all": "text+decide+rescue", "all+cgplan": "text+decide+rescue+plan+pestat+cgplan", "all+cgplan+cgprep": "text+decide+rescue+plan+pestat+cgplan+cgprep"}.get(a.bit, a.bit).split("+"))
     bits = (getattr(bm2, "SAM_F_DEVICE_TEXT", 0) if "text" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_DECIDE", 0) if "decide" in on else 0) | \
            (getattr(bm2, "SAM_F_DEVICE_RESCUE", 0) if "rescue" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PLAN", 0) if "plan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_PESTAT", 0) if "pestat" in on else 0) | \
-           (getattr(bm2, "SAM_F_DEVICE_CGPLAN", 0) if "cgplan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_SEMARK", 0) if "semark" in on else 0)
+           (getattr(bm2, "SAM_F_DEVICE_CGPLAN", 0) if "cgplan" in on else 0) | (getattr(bm2, "SAM_F_DEVICE_SEMARK", 0) if "semark" in on else 0) | \
+           (getattr(bm2, "SAM_F_DEVICE_CGPREP", 0) if "cgprep" in on else 0)
     flag = {"off": 0, "on": bits}
     bufs = {v: bm2.Pinned(int(3 * (int(ch.f.n_bases) + 200 * ch.n_reads))) for v in variants}     # page-locked, as the pipeline's text buffers are
     so = {v: bm2.default_sam_opt(n_threads=a.threads, flag=flag[v]) for v in variants}
@@ -157,7 +162,7 @@ def main():
     wall = {v: [] for v in variants}
     cpu = {v: [] for v in variants}
     ph = {v: [] for v in variants}
-    counters, first, decided, rescued, planned_dev, model_dev, cgplan_dev, semark_dev = None, None, None, None, None, None, None, None
+    counters, first, decided, rescued, planned_dev, model_dev, cgplan_dev, semark_dev, cgprep_dev = None, None, None, None, None, None, None, None, None
     os.environ["BM2_TAIL_PROF"] = "1"
     for rep in range(2 + a.calls):
         texts = {}
@@ -181,6 +186,8 @@ def main():
                 cgplan_dev = bm2.sam_cigar_plan_stats() + bm2.sam_cigar_stats()
             if v == "on" and "semark" in on:
                 semark_dev = bm2.sam_se_mark_stats() + bm2.sam_cigar_stats()
+            if v == "on" and "cgprep" in on:
+                cgprep_dev = bm2.sam_cigar_prep_stats()
             if rep >= 2:
                 wall[v].append(dt * 1e3); cpu[v].append(dc); ph[v].append(phases(err.text))
         if len(variants) == 2:
@@ -228,6 +235,10 @@ def main():
         lists, hits, heavy, planned, used, missed = semark_dev
         mine["semark_stats"] = {"lists": lists, "hits": hits, "lists_heavy": heavy, "planned": planned, "used": used, "missed": missed}
         mine["semark_pcie"] = {"up": 20 * hits + 8 * (lists + 1), "down": 32 * hits + 8, "cgplan_up_saved": 16 * hits if "cgplan" in on else 0}
+    if cgprep_dev is not None:                                   # (cgprep.hip: 40 B a task and 12 B a read up INSTEAD of 76 B a task; 72 B of totals and error words down)
+        tasks, shape, up, fallbacks = cgprep_dev
+        mine["cgprep_stats"] = {"tasks": tasks, "ring": shape[0], "row": shape[1], "global": shape[2], "flat": shape[3], "bytes_up": up, "host_fallbacks": fallbacks}
+        mine["cgprep_pcie"] = {"up": up, "up_without_the_bit": 76 * tasks, "down": 72}
     res.update(mine) if not a.parent_lib else res.update({"new": mine})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1, sort_keys=True)

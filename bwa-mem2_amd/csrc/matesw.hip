@@ -167,6 +167,10 @@ extern "C" int bm2_ksw_align2_dev(bm2_ctx *c, int32_t n, const uint8_t *seqs, in
         bm2_set_error("bm2_ksw_align2_dev: bad argument");
         return BM2_EINVAL;
     }
+    // what bm2_ksw_align2 refuses, before anything is launched or written (the tail's hooks call ksw_batch_run themselves: mates are never empty)
+    if (e_del <= 0 || e_ins <= 0) { bm2_set_error("bm2_ksw_align2_dev: bad argument"); return BM2_EINVAL; }
+    for (int i = 0; i < n; ++i)
+        if (q_len[i] <= 0 || t_len[i] < 0) { bm2_set_error("bm2_ksw_align2_dev: pair %d has an empty query", i); return BM2_EINVAL; }
     return ksw_batch_run(c, n, seqs, seq_bytes, nullptr, q_off, q_len, t_off, t_len, xtra, mat, o_del, e_del, o_ins, e_ins, out);
 }
 

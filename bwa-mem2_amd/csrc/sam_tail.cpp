@@ -908,9 +908,10 @@ KswResult ksw_align2(int qlen, const uint8_t *query, int tlen, const uint8_t *ta
     KswResult r = byte ? ksw_pass<16>(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, xtra)
                        : ksw_pass<8>(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, xtra);
     if ((xtra & KSW_XSTART) == 0 || ((xtra & KSW_XSUBO) && r.score < (xtra & 0xffff))) return r;
+    if (r.qe < 0) return r;                                     // a saturated byte pass has no query end: no start pass (the reference's is undefined there; matesw_dev.h skips it too)
     std::vector<uint8_t> rq(query, query + r.qe + 1), rt(target, target + tlen);
     std::reverse(rq.begin(), rq.end());
-    std::reverse(rt.begin(), rt.begin() + r.te + 1);            // only the first te+1 bases are reversed; the rest of the target stays
+    std::reverse(rt.begin(), rt.begin() + (r.te + 1));          // only the first te+1 bases are reversed; the rest of the target stays (te = -1 of an empty target: none)
     const int x2 = KSW_XSTOP | r.score;
     const KswResult rr = byte ? ksw_pass<16>(r.qe + 1, rq.data(), tlen, rt.data(), mat, o_del, e_del, o_ins, e_ins, x2)
                               : ksw_pass<8>(r.qe + 1, rq.data(), tlen, rt.data(), mat, o_del, e_del, o_ins, e_ins, x2);
@@ -2218,8 +2219,9 @@ extern "C" int bm2_ksw_align2(int32_t n, const uint8_t *seqs, const int64_t *q_o
     if (n < 0 || (n > 0 && (!seqs || !q_off || !q_len || !t_off || !t_len || !xtra || !mat || !out)) || e_del <= 0 || e_ins <= 0) {
         bm2_set_error("bm2_ksw_align2: bad argument"); return BM2_EINVAL;
     }
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)                                 // (refused before anything is written, as the device twin does)
         if (q_len[i] <= 0 || t_len[i] < 0) { bm2_set_error("bm2_ksw_align2: pair %d has an empty query", i); return BM2_EINVAL; }
+    for (int i = 0; i < n; ++i) {
         const KswResult r = ksw_align2(q_len[i], seqs + q_off[i], t_len[i], seqs + t_off[i], mat, o_del, e_del, o_ins, e_ins, xtra[i]);
         out[i].score = r.score; out[i].te = r.te; out[i].qe = r.qe; out[i].score2 = r.score2; out[i].te2 = r.te2; out[i].tb = r.tb; out[i].qb = r.qb;
     }

@@ -237,13 +237,18 @@ void bm2_sam_rescue_stats(int64_t *planned, int64_t *used, int64_t *missed);
  * (score, target end, query end, second-best score / its target end outside the best's neighbourhood) and, with KSW_XSTART, a
  * reverse pass for the start.  This is the HOST implementation (the SSE2 kernel's striping is observable and kept): the oracle of the
  * device kernel below and the code that aligns the few rescues a pair asks for outside its chunk's batch.  xtra = KSW_X* flags | minimum score, as mem_matesw builds it
- * (bwamem_pair.cpp:205).  out[i] = { score, te, qe, score2, te2, tb, qb }. */
+ * (bwamem_pair.cpp:205).  out[i] = { score, te, qe, score2, te2, tb, qb }.
+ * Refused with BM2_EINVAL before anything is written: a gap extension penalty <= 0 ("bad argument"), a pair with q_len <= 0 or
+ * t_len < 0 ("pair <i> has an empty query", the lowest such i).  A byte pass (KSW_XBYTE) that saturates answers score 255 with
+ * qe = -1 and no second-best hit; the start pass of KSW_XSTART is then skipped (tb = qb = -1): the reference's is undefined there. */
 typedef struct { int32_t score, te, qe, score2, te2, tb, qb; } bm2_ksw_result;
 int bm2_ksw_align2(int32_t n, const uint8_t *seqs, const int64_t *q_off, const int32_t *q_len, const int64_t *t_off, const int32_t *t_len,
                    const int32_t *xtra, const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins, bm2_ksw_result *out);
 
 /* The same on the device (matesw.hip: one task per 16-lane row, the lanes of the reference's SSE2 register).  seq_bytes = size of
- * seqs.  Results identical to bm2_ksw_align2. */
+ * seqs.  Results identical to bm2_ksw_align2, and the same refusals in the same words under its own name: nothing is launched or
+ * written.  Beyond them: BM2_EUNSUP for a batch with a query of more than 448 bases on word lanes or 896 on byte lanes (its rows do not
+ * fit the LDS layout). */
 int bm2_ksw_align2_dev(bm2_ctx *c, int32_t n, const uint8_t *seqs, int64_t seq_bytes, const int64_t *q_off, const int32_t *q_len,
                        const int64_t *t_off, const int32_t *t_len, const int32_t *xtra, const int8_t mat[25], int o_del, int e_del,
                        int o_ins, int e_ins, bm2_ksw_result *out);
